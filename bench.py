@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
-"""bench.py -- headline benchmark on MI355X: HGEMM fp16 TFLOPS at M=N=K=4096 (BASELINE.json metric),
-with FA2 forward TFLOPS (D=64, D=128) and the rocBLAS row reported beside it.
+"""bench.py -- headline benchmark on MI355X: HGEMM fp16 TFLOPS at M=N=K=4096 (BASELINE.json metric);
+with --full, FA2 forward TFLOPS (D=64, D=128), the rocBLAS row and the other side rows reported beside it.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the result line; --dump-outputs DIR also writes C of the
+last timed step (rank 0) to DIR/c.npy. Everything else -- vendor rows, FA2 rooflines, the CPU baseline, the rocprofv3
+counter passes and the per-config rows of bench_configs.py -- runs only with --full (single-GPU run).
 
 A "step" is one pass of the hot path over one batch of synthetic input: ONE 4096^3 HGEMM launch
 (reference config C3: kernels/hgemm/hgemm.py --mma --MNK 4096, the
@@ -14,7 +18,7 @@ Output on rank 0 (the driver keeps an 8 KB stdout tail and parses
   * every measured row in full -> bench_detail.json (repository root, and gpurun_out/ when it exists);
   * short one-row-per-kernel lines on stdout, as the reference scripts print (kernels/hgemm/hgemm.py:142-168);
   * the LAST stdout line: one compact JSON object (< 4 KB, `headline_line`) with metric / value / ms_per_step / config /
-    roofline / cpu_baseline and a digest of the side rows. tests/test_bench_line.py holds the size bound.
+    roofline and, with --full, cpu_baseline and a digest of the side rows. tests/test_bench_line.py holds the size bound.
 """
 import argparse
 import json
@@ -37,9 +41,13 @@ def parse():
     p.add_argument("--mnk", type=int, default=4096)
     p.add_argument("--stages", type=int, default=2)
     p.add_argument("--prewarm", type=float, default=0.6, help="seconds of untimed back-to-back launches before warmup")
-    p.add_argument("--no-extras", action="store_true", help="skip FA2 / rocBLAS / CPU baseline side measurements")
-    p.add_argument("--no-pmc", action="store_true", help="do not re-run the headline kernel under rocprofv3 --pmc for this box's counters (3 child passes, ~20 s)")
-    p.add_argument("--no-configs", action="store_true", help="skip the per-config rows (C1, C2, 8192^3, stage sweeps, bandwidth kernels)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run the side measurements: vendor GEMM / FA2 / SDPA rows, CPU baseline, rocprofv3 counter "
+                        "passes, per-config rows (single-GPU run only; ~2 min)")
+    p.add_argument("--dump-outputs", metavar="DIR", help="write C of the last timed step to DIR/c.npy (float32; a fixed row sample above 4M elements)")
+    p.add_argument("--no-extras", action="store_true", help="with --full: skip FA2 / rocBLAS / CPU baseline side measurements")
+    p.add_argument("--no-pmc", action="store_true", help="with --full: do not re-run the headline kernel under rocprofv3 --pmc for this box's counters (3 child passes, ~20 s)")
+    p.add_argument("--no-configs", action="store_true", help="with --full: skip the per-config rows (C1, C2, 8192^3, stage sweeps, bandwidth kernels)")
     p.add_argument("--launch", choices=["graph", "eager"], default="eager",
                    help="how the K timed steps reach the GPU: K eager launches from Python (default: host enqueue 9.5 us per step against a "
                         "94 us kernel) or one hipGraph holding the K launches (measured slower: +26 us per kernel node, 1141 vs 1442 TF)")
@@ -153,6 +161,8 @@ def main():
     elapsed = time.perf_counter() - t0
     elapsed = bu.max_over_ranks(elapsed, dist, None)
     ev_ms = ev0.elapsed_time(ev1) / args.steps  # HIP events on the launch stream, over the SAME timed region
+    if args.dump_outputs and rank == 0:  # before the side rows, which write into c
+        dump_outputs(args.dump_outputs, c)
 
     flops = bu.hgemm_flops(M, N, K)
     ms_per_step = elapsed / args.steps * 1e3
@@ -192,7 +202,7 @@ def main():
         "roofline": roofline,
     }
 
-    if rank == 0 and world == 1 and not args.no_extras:  # side measurements only in the single-GPU run
+    if args.full and rank == 0 and world == 1 and not args.no_extras:  # side measurements only in the single-GPU run
         extras = {"timing": "side rows: 0.2-0.3 s pre-warm, then ONE event-timed region of back-to-back launches (ours and "
                             "the vendor's alike; no best-of-N)"}
 
@@ -459,6 +469,26 @@ def emit(out):
         print("# detail rows unavailable: %s" % str(e)[:120])
     sys.stdout.flush()
     print(headline_line(out), flush=True)
+
+
+DUMP_ELEMS = 1 << 22  # 16 MB of float32 per dump; the whole 4096^2 C would be 64 MB
+
+
+def dump_rows(M, N):
+    """Rows of an M x N output that --dump-outputs writes: all of them up to DUMP_ELEMS elements, else a sample of whole rows
+    drawn from a fixed seed, in ascending order (the same rows for the same shape in every run and every build)."""
+    if M * N <= DUMP_ELEMS:
+        return torch.arange(M)
+    g = torch.Generator().manual_seed(0)
+    return torch.randperm(M, generator=g)[:max(1, DUMP_ELEMS // N)].sort().values
+
+
+def dump_outputs(dirname, c):
+    """C as the timed path left it -> DIR/c.npy, float32, rows dump_rows(M, N)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    rows = dump_rows(*c.shape).to(c.device)
+    np.save(os.path.join(dirname, "c.npy"), c.index_select(0, rows).float().cpu().numpy())
 
 
 def cpu_baseline(a, b, M, N, K):

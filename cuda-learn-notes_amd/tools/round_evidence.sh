@@ -22,9 +22,9 @@ timeout 120 python -m pytest tests/test_gpu_flash_attn.py -m gpu -x -q -k golden
 timeout 1500 python -m pytest tests -m gpu -q --timeout 120 > $OUT/${TAG}_pytest_gpu.log 2>&1; RC=$?; echo "pytest rc=$RC"; tail -3 $OUT/${TAG}_pytest_gpu.log
 if [ $RC -gt 1 ]; then echo "pytest aborted"; exit 8; fi
 # (round 5: stdout = one short row per kernel, then the compact headline object as the LAST line; the full result is bench_detail.json)
-timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_20steps.log 2> $OUT/${TAG}_bench_20steps.err; echo "bench20 rc=$?"
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_bench_20steps.log 2> $OUT/${TAG}_bench_20steps.err; echo "bench20 rc=$?"
 tail -1 $OUT/${TAG}_bench_20steps.log > $OUT/${TAG}_bench_20steps.json; cp $OUT/bench_detail.json $OUT/${TAG}_bench_detail_20steps.json
-timeout 600 python bench.py > $OUT/${TAG}_bench_default.log 2> $OUT/${TAG}_bench_default.err; echo "bench rc=$?"
+timeout 600 python bench.py --full > $OUT/${TAG}_bench_default.log 2> $OUT/${TAG}_bench_default.err; echo "bench rc=$?"
 tail -1 $OUT/${TAG}_bench_default.log > $OUT/${TAG}_bench_default.json; cp $OUT/bench_detail.json $OUT/${TAG}_bench_detail_default.json
 timeout 900 bash $T/profile_round.sh $TAG > $OUT/${TAG}_profile_round.log 2>&1; echo "profile_round rc=$?"
 timeout 600 bash $T/fa_trace.sh $TAG > $OUT/${TAG}_fa_trace.log 2>&1; echo "fa_trace rc=$?"

@@ -92,3 +92,31 @@ def test_emit_prints_headline_last_and_rows_are_short(tmp_path, monkeypatch):
     # the driver's 8 KB tail always holds the whole final line
     tail = buf.getvalue()[-8192:]
     assert json.loads(tail.rstrip("\n").split("\n")[-1])["metric"].startswith("HGEMM")
+
+
+def test_plain_run_takes_no_side_rows_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_rows_are_a_fixed_sample_under_64_mb():
+    import torch
+    assert torch.equal(bench.dump_rows(1024, 1024), torch.arange(1024))  # small outputs are written whole
+    r = bench.dump_rows(4096, 4096)
+    assert torch.equal(r, bench.dump_rows(4096, 4096))  # the same rows in every run
+    assert r.numel() * 4096 * 4 <= bench.DUMP_ELEMS * 4 <= 64 << 20
+    assert r.numel() == len(set(r.tolist())) and bool((r[1:] > r[:-1]).all()) and 0 <= int(r[0]) and int(r[-1]) < 4096
+
+
+def test_dump_outputs_writes_float32_rows_of_c(tmp_path):
+    import numpy as np
+    import torch
+    c = torch.randn(4096, 2048, generator=torch.Generator().manual_seed(3)).half()
+    bench.dump_outputs(str(tmp_path / "out"), c)
+    x = np.load(tmp_path / "out" / "c.npy")
+    assert x.dtype == np.float32 and x.shape == (2048, 2048)
+    assert np.array_equal(x, c[bench.dump_rows(4096, 2048)].float().numpy())
