@@ -23,3 +23,10 @@ def hgemm_lib():
 
 def flash_attn_lib():
     return load("flash_attn")
+
+
+def fa2_fwd_causal(Q, K, V, O, stages=2):
+    """Causal FlashAttention-2 forward (mask key <= query) into O; fp16 [B,H,N,D], D in {64, 128}, N % 256 == 0.
+    C entry: cln_fa2_fwd_causal (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_fwd_causal(Q, K, V, O, stages)

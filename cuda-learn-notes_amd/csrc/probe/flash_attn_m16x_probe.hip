@@ -5,11 +5,21 @@
 // steps into v_pk_add_f32, which drags the exponentials of a whole phase behind its last MFMA and is slower than two
 // plain adds beside MFMAs (MI355X_MICROARCH.md, per-instruction constants). Linked into the probe library only.
 #include "flash_attn_m16x.cuh"
+#include "flash_attn_causal.cuh"
 #include "flash_attn_m16s.cuh"
 #include "flash_attn_m32x.cuh"
 #include "flash_attn_m16x_api.h"
 
 namespace fa2 {
+
+// the causal kernel (flash_attn_causal.cuh, stages = 2) in each launch order M16X_ORDER_* (the product ships one of them: flash_attn_causal.hip)
+int m16x_causal_probe_run(int D, int order, const void* q, const void* k, const void* v, void* o, int B, int H, int N, hipStream_t s) {
+  if (N % 256 != 0) return CLN_ERR_UNSUPPORTED;
+  if (order == M16X_ORDER_PLAIN) return fa2c::run_causal<M16X_ORDER_PLAIN>(D, false, q, k, v, o, B, H, N, s);
+  if (order == M16X_ORDER_HEAVY) return fa2c::run_causal<M16X_ORDER_HEAVY>(D, false, q, k, v, o, B, H, N, s);
+  if (order == M16X_ORDER_HEAD_REV) return fa2c::run_causal<M16X_ORDER_HEAD_REV>(D, false, q, k, v, o, B, H, N, s);
+  return CLN_ERR_UNSUPPORTED;
+}
 
 // code = 16 * (NDEF - 1) + OX for the 32-rows-per-wave forms; 96 + ...: fragment prefetch depth 4 instead of 8 (D = 64);
 // 120 + 16 * (NDEF - 1) + OX: 64 rows per wave (D = 64, 64-key tiles)

@@ -10,6 +10,7 @@ Reference bindings mirrored (checks and messages):
   CHECK_TORCH_TENSOR_SHAPE -> RuntimeError("Tensor size mismatch!")          kernels/hgemm/naive/hgemm.cu:778-782
   head-dim switch default  -> RuntimeError("headdim not support!")           flash_attn_mma_share_qkv.cu:860,:882
 """
+import ctypes
 import os
 import threading
 import types
@@ -577,3 +578,31 @@ def fa2_variant(D_nw_vt_opt_abl, Q, K, V, O):
     fn = _loader.load_so("libcln_amd_probe.so").cln_fa2_variant
     rc = fn(D, nw, vt, opt, abl, Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), B, H, N, _stream())
     _raise("cln_fa2_variant", rc, "variant not instantiated / shape not supported")
+
+
+_causal_fn = None
+
+
+def fa2_fwd_causal(Q, K, V, O, stages=2):
+    """Causal FlashAttention-2 forward (mask key <= query, scale 1/sqrt(D)) into O: fp16 [B,H,N,D] tensors, D in {64, 128},
+    N a multiple of 256. C entry cln_fa2_fwd_causal (include/cln_amd_ext.h); no CPU path."""
+    global _causal_fn
+    if _causal_fn is None:
+        fn = _loader.load_so("libcln_amd.so").cln_fa2_fwd_causal
+        fn.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 + [ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+        _causal_fn = fn
+    for t in (Q, K, V, O):
+        _check_dtype(t, torch.float16)
+    _check_dev(Q, K, V, O)
+    if Q.dim() != 4:
+        raise RuntimeError("Tensor size mismatch!")
+    B, H, N, D = Q.shape
+    for t in (K, V, O):
+        _check_shape(t, B, H, N, D)
+    rc = _causal_fn(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), B, H, N, D, int(stages), _stream())
+    if rc == -2:
+        if D not in (64, 128):
+            raise RuntimeError("fa2_fwd_causal: headdim %d not supported (64 or 128)" % D)
+        raise RuntimeError("fa2_fwd_causal: seqlen %d must be a multiple of 256" % N)
+    _raise("fa2_fwd_causal", rc)
