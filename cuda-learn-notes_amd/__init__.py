@@ -30,3 +30,53 @@ def fa2_fwd_causal(Q, K, V, O, stages=2):
     C entry: cln_fa2_fwd_causal (include/cln_amd_ext.h). Not a reference name."""
     from . import host
     return host.fa2_fwd_causal(Q, K, V, O, stages)
+
+
+def fa2_fwd_lse(Q, K, V, O, LSE, causal=False, stages=2):
+    """FlashAttention-2 forward into O that also writes the row log-sum-exp LSE (fp32 [B,H,N], natural log); fp16 [B,H,N,D],
+    D in {64, 128}, N % 256 == 0. C entries cln_fa2_fwd_lse / cln_fa2_fwd_causal_lse (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_fwd_lse(Q, K, V, O, LSE, causal, stages)
+
+
+def fa2_bwd(Q, K, V, O, dO, LSE, dQ, dK, dV, delta=None, causal=False):
+    """FlashAttention-2 backward into dQ, dK, dV from the forward's O and LSE (fa2_fwd_lse); deterministic. C entries cln_fa2_bwd /
+    cln_fa2_bwd_causal (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_bwd(Q, K, V, O, dO, LSE, dQ, dK, dV, delta, causal)
+
+
+def fa2_attention(q, k, v, causal=False):
+    """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
+    fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""
+    return _attention_fn().apply(q, k, v, bool(causal))
+
+
+_ATTN_FN = None
+
+
+def _attention_fn():
+    global _ATTN_FN
+    if _ATTN_FN is None:
+        import torch
+
+        class FA2Attention(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, q, k, v, causal):
+                q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+                o = torch.empty_like(q)
+                lse = torch.empty(q.shape[:3], dtype=torch.float32, device=q.device)
+                fa2_fwd_lse(q, k, v, o, lse, causal)
+                ctx.save_for_backward(q, k, v, o, lse)
+                ctx.causal = causal
+                return o
+
+            @staticmethod
+            def backward(ctx, grad_out):
+                q, k, v, o, lse = ctx.saved_tensors
+                dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+                fa2_bwd(q, k, v, o, grad_out.contiguous(), lse, dq, dk, dv, causal=ctx.causal)
+                return dq, dk, dv, None
+
+        _ATTN_FN = FA2Attention
+    return _ATTN_FN

@@ -17,7 +17,9 @@ __global__ __launch_bounds__(512, 2) void fa2_fwd_m16x_causal_kernel(const half_
                                                                      int N, int n_qblk, int n_heads, float scale_log2e) {
   constexpr int RPW_ = 32, BC_ = 128;
   constexpr bool VT = false, CAUSAL = true;
+  constexpr bool LSE = false;
   [[maybe_unused]] unsigned long long* stamps = nullptr;
+  [[maybe_unused]] float* lse = nullptr;
 #include "flash_attn_m16x_body.inc"
 }
 

@@ -91,6 +91,8 @@ __global__ __launch_bounds__(512, 2) void fa2_fwd_m16x_kernel(const half_t* __re
                                                               int N, int n_qblk, int n_heads, float scale_log2e, unsigned long long* stamps) {
   constexpr bool CAUSAL = false;
   constexpr int ORDER = M16X_ORDER_PLAIN;
+  constexpr bool LSE = false;
+  [[maybe_unused]] float* lse = nullptr;
 #include "flash_attn_m16x_body.inc"
 }
 

@@ -1,8 +1,10 @@
 // Body of the sum-checked optimistic-softmax attention kernels (flash_attn_m16x.cuh), included textually by each __global__ that runs it:
-// fa2::fa2_fwd_m16x_kernel (CAUSAL = false) and fa2c::fa2_fwd_m16x_causal_kernel (flash_attn_causal.cuh, CAUSAL = true). A textual body
+// fa2::fa2_fwd_m16x_kernel (CAUSAL = false), fa2c::fa2_fwd_m16x_causal_kernel (flash_attn_causal.cuh, CAUSAL = true) and
+// fa2b::fa2_fwd_m16x_lse_kernel (flash_attn_fwd_lse.hip, LSE = true, either CAUSAL). A textual body
 // and not a force-inlined __device__ function: hipcc simplifies a callee on its own before inlining it, which renumbers registers and
 // reorders a few scalar adds of the plain kernels -- this way their instruction stream stays exactly the one of the kernel this was cut from.
-// In scope: template parameters D_, RPW_, BC_, PD, NDEF, OX, VT; constants CAUSAL, ORDER (M16X_ORDER_*); the kernel arguments.
+// In scope: template parameters D_, RPW_, BC_, PD, NDEF, OX, VT; constants CAUSAL, ORDER (M16X_ORDER_*), LSE; the kernel arguments
+// (with LSE: `lse`, fp32 [B,H,N], the row's natural-log log-sum-exp of the scaled scores, written by the epilogue).
 // No include guard: included once per kernel body.
   constexpr bool STAMP = (OX & M16X_STAMP) != 0;
   unsigned long long st_rt[4] = {0, 0, 0, 0}, st_mt[4] = {0, 0, 0, 0};
@@ -487,6 +489,11 @@
       l_tot = __uint_as_float(s32[0]) + __uint_as_float(s32[1]);
     }
     const float inv = 1.0f / l_tot;
+    if constexpr (LSE) {
+      // m_run is the row's reference in log2 units of the pre-scaled scores and l_tot the row sum relative to it (the reference
+      // need not be the true maximum): ln sum_j exp(q.k_j / sqrt(D)) = ln 2 (m_run + log2 l_tot). After the swaps every lane of the row holds both.
+      if (g4_e == 0) lse[(size_t)head_i * N + q_row0 + qb * 16 + i16_e] = 0.69314718055994531f * (m_run[qb] + log2f(l_tot));
+    }
 #pragma unroll
     for (int b = 0; b < NDB; ++b) {
       h4 o;

@@ -606,3 +606,70 @@ def fa2_fwd_causal(Q, K, V, O, stages=2):
             raise RuntimeError("fa2_fwd_causal: headdim %d not supported (64 or 128)" % D)
         raise RuntimeError("fa2_fwd_causal: seqlen %d must be a multiple of 256" % N)
     _raise("fa2_fwd_causal", rc)
+
+
+_lse_fns = {}
+
+
+def _ext_fn(name, argtypes):
+    fn = _lse_fns.get(name)
+    if fn is None:
+        fn = getattr(_loader.load_so("libcln_amd.so"), name)
+        fn.argtypes = argtypes
+        fn.restype = ctypes.c_int
+        _lse_fns[name] = fn
+    return fn
+
+
+def _check_bh(name, B, H, N, D, rc):
+    if rc == -2:
+        if D not in (64, 128):
+            raise RuntimeError("%s: headdim %d not supported (64 or 128)" % (name, D))
+        raise RuntimeError("%s: seqlen %d must be a multiple of 256" % (name, N))
+    _raise(name, rc)
+
+
+def fa2_fwd_lse(Q, K, V, O, LSE, causal=False, stages=2):
+    """FlashAttention-2 forward (scale 1/sqrt(D); causal: mask key <= query) into O, and the row log-sum-exp into LSE (fp32 [B,H,N],
+    natural log): fp16 [B,H,N,D] tensors, D in {64, 128}, N a multiple of 256. C entries cln_fa2_fwd_lse / cln_fa2_fwd_causal_lse
+    (include/cln_amd_ext.h); no CPU path."""
+    name = "cln_fa2_fwd_causal_lse" if causal else "cln_fa2_fwd_lse"
+    fn = _ext_fn(name, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_void_p])
+    for t in (Q, K, V, O):
+        _check_dtype(t, torch.float16)
+    _check_dtype(LSE, torch.float32)
+    _check_dev(Q, K, V, O, LSE)
+    if Q.dim() != 4:
+        raise RuntimeError("Tensor size mismatch!")
+    B, H, N, D = Q.shape
+    for t in (K, V, O):
+        _check_shape(t, B, H, N, D)
+    _check_shape(LSE, B, H, N)
+    rc = fn(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), LSE.data_ptr(), B, H, N, D, int(stages), _stream())
+    _check_bh("fa2_fwd_lse", B, H, N, D, rc)
+
+
+def fa2_bwd(Q, K, V, O, dO, LSE, dQ, dK, dV, delta=None, causal=False):
+    """FlashAttention-2 backward into dQ, dK, dV (fp16 [B,H,N,D]) from Q, K, V, O, dO (fp16 [B,H,N,D]) and the forward's LSE (fp32 [B,H,N],
+    fa2_fwd_lse). delta: fp32 [B,H,N] scratch that receives rowsum(dO * O); allocated here on the current stream when None. Deterministic.
+    C entries cln_fa2_bwd / cln_fa2_bwd_causal (include/cln_amd_ext.h); no CPU path."""
+    name = "cln_fa2_bwd_causal" if causal else "cln_fa2_bwd"
+    fn = _ext_fn(name, [ctypes.c_void_p] * 10 + [ctypes.c_int] * 4 + [ctypes.c_void_p])
+    for t in (Q, K, V, O, dO, dQ, dK, dV):
+        _check_dtype(t, torch.float16)
+    _check_dtype(LSE, torch.float32)
+    _check_dev(Q, K, V, O, dO, LSE, dQ, dK, dV)
+    if Q.dim() != 4:
+        raise RuntimeError("Tensor size mismatch!")
+    B, H, N, D = Q.shape
+    for t in (K, V, O, dO, dQ, dK, dV):
+        _check_shape(t, B, H, N, D)
+    _check_shape(LSE, B, H, N)
+    if delta is None:
+        delta = torch.empty((B, H, N), dtype=torch.float32, device=Q.device)
+    _check_dtype(delta, torch.float32)
+    _check_dev(delta)
+    _check_shape(delta, B, H, N)
+    rc = fn(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), LSE.data_ptr(), delta.data_ptr(),
+            dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), B, H, N, D, _stream())
+    _check_bh("fa2_bwd", B, H, N, D, rc)

@@ -17,6 +17,27 @@ extern "C" {
  */
 int cln_fa2_fwd_causal(const void* q, const void* k, const void* v, void* o, int B, int H, int N, int D, int stages, void* stream);
 
+/* ---- Forwards that also write the row log-sum-exp, the input of the backward below (non-causal / causal).
+ * lse: fp32 [B,H,N], 16-byte aligned; lse[b,h,i] = ln sum_{j allowed} exp(Q_i . K_j / sqrt(D)) (natural log). O is bit-identical to
+ * cln_fa2_fwd_causal (causal) and to the plain 32-rows-per-wave kernel (non-causal). Same support, stages and statuses as
+ * cln_fa2_fwd_causal; -1 also when o or lse equals an input pointer or each other. cln_describe names the kernel.
+ */
+int cln_fa2_fwd_lse(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int N, int D, int stages, void* stream);
+int cln_fa2_fwd_causal_lse(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int N, int D, int stages, void* stream);
+
+/* ---- FlashAttention-2 backward (non-causal / causal; the mask as in the forward): dq, dk, dv (fp16 [B,H,N,D]) from q, k, v, o, dout
+ * (fp16 [B,H,N,D]) and lse (fp32 [B,H,N], from cln_fa2_fwd_lse / cln_fa2_fwd_causal_lse). delta: caller-provided fp32 [B,H,N]
+ * scratch, written with rowsum(dout o o) and read back by the second kernel. Two kernels on `stream`; every output element is summed
+ * by one workgroup in a fixed order, so results are bit-repeatable.
+ * Supported: D in {64, 128}, N a multiple of 256. Returns 0, -1 (null / misaligned pointer, non-positive B, H, N or D, an output
+ * pointer equal to an input pointer or to another output), -2 (other D, N % 256 != 0, grid too large) -- both checked before any
+ * device access -- or -3 (launch error). cln_describe names both kernels; the stages argument is ignored.
+ */
+int cln_fa2_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, float* delta,
+                void* dq, void* dk, void* dv, int B, int H, int N, int D, void* stream);
+int cln_fa2_bwd_causal(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, float* delta,
+                       void* dq, void* dk, void* dv, int B, int H, int N, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
