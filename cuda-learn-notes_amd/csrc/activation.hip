@@ -7,9 +7,12 @@
 // per-lane access the rung name states (4 B, 16 B; 2 B, 4 B, 8 x 2 B, 16 B); capped grid-stride grid.
 // Arithmetic is fp32 for every rung (the reference's f16 rungs use half intrinsics: hexp, __hdiv ...): the
 // result is rounded to fp16 once, which is at least as close to the script's torch column as the reference's own
-// half arithmetic. Constants follow the reference kernels: sigmoid / gelu clamp their argument to
-// +-88.3762626647949 (sigmoid.cu:19-20, gelu.cu:19-20), gelu is the tanh approximation (gelu.cu:46-48), elu alpha
+// half arithmetic. Constants follow the reference kernels: sigmoid clamps its argument to
+// +-88.3762626647949 (sigmoid.cu:19-20), gelu is the tanh approximation (gelu.cu:46-48), elu alpha
 // = 1 (elu.cu:19), hardswish thresholds +-3 (hardswish.cu:12-13), hardshrink lambda = 0.5 (hardshrink.cu:19).
+// ON PURPOSE NOT the reference's: gelu.cu:19-20 also clamps gelu's INPUT to +-88.376 and multiplies by the clamped value, so its gelu(x) = 88.376
+// for every x above that (fp16 inputs reach 65504). Here gelu follows the script's torch column, torch.nn.GELU("tanh"): x for large x, -0 for
+// large -x (the parity target, as with rope; tests/test_gpu_bw_edges.py sweeps every finite half value and the fp32 range).
 #include "common.h"
 
 namespace {
@@ -29,8 +32,10 @@ struct Sigmoid {
 struct Gelu {
   // tanh form (reference gelu.cu GELU_OPS, torch.nn.GELU("tanh")): 0.5 x (1 + tanh u) = x / (1 + e^(-2u)), u = sqrt(2/pi) (x + 0.044715 x^3) --
   // one exponential and one reciprocal instead of tanhf's ~25-instruction expansion (f16x8_pack 4096^2: 15.5 us, VALU-bound, with tanhf)
+  // x itself is NOT clamped (the reference's gelu.cu:19-20 clamps it, so its gelu(100) is 88.376): the parity target is the script's torch column,
+  // which returns x for large x and -0 for large -x. No clamp is needed for that: x^3 overflows to +-inf, e^(-2u) to 0 or +inf, the reciprocal to
+  // 1 or 0, and x * 0 is -0 for every finite negative x. (Clamping the exponent at +88.376 instead would leave 1 / e^88.376 = 4e-39, times x = -3e38.)
   static __device__ __forceinline__ float f(float x) {
-    x = fminf(fmaxf(x, -88.3762626647949f), 88.3762626647949f);
     const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
     return x * rcp1(1.0f + __expf(-2.0f * u));
   }

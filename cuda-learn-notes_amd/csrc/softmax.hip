@@ -141,7 +141,10 @@ __global__ void softmax_row_kernel(const T* __restrict__ x, T* __restrict__ y, i
       for (int e = 0; e < VEC; ++e) {
         const float v = r.x[i][e];
         const float mn = fmaxf(m, v);
-        d = d * __expf(m - mn) + __expf(v - mn);  // m == mn == -inf only for all-padding lanes
+        // while the lane has seen nothing but -inf (padding, or the masked head of a row) mn is -inf and m - mn would be NaN: rescale about 0
+        // instead, which leaves d = 0 * 0 + 0. A finite mn takes the same operations as before.
+        const float ms = (mn == -INFINITY) ? 0.f : mn;
+        d = d * __expf(m - ms) + __expf(v - ms);
         m = mn;
       }
     if (m == -INFINITY) d = 0.f;

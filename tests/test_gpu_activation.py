@@ -17,7 +17,7 @@ def lib(built, dev):
 @pytest.mark.parametrize("op", OPS)
 @pytest.mark.parametrize("shape", [(1024, 1024), (7, 24), (3, 5, 64)])
 def test_activation_matches_oracle(lib, dev, oracle, op, shape):
-    g = torch.Generator().manual_seed(hash(op) % 1000)
+    g = torch.Generator().manual_seed(OPS.index(op))
     x = torch.randn(*shape, generator=g) * 3.0
     x.view(-1)[:6] = torch.tensor([0.0, -0.0, 0.5, -0.5, 3.0, -3.0])  # thresholds of hardshrink / hardswish
     for rung in RUNGS:
