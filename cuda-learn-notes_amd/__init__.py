@@ -46,6 +46,19 @@ def fa2_bwd(Q, K, V, O, dO, LSE, dQ, dK, dV, delta=None, causal=False):
     return host.fa2_bwd(Q, K, V, O, dO, LSE, dQ, dK, dV, delta, causal)
 
 
+def fa2_decode(q, k_cache, v_cache, seqlens, out, lse=None, workspace=None):
+    """Single-query (decode) attention over a KV cache into out: q, out fp16 [B,H,D], caches fp16 [B,H,Nmax,D], seqlens int32 [B] on the GPU,
+    lse fp32 [B,H] or None; D in {64, 128}, any Nmax. C entry cln_fa2_decode (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_decode(q, k_cache, v_cache, seqlens, out, lse, workspace)
+
+
+def fa2_decode_plan(B, H, Nmax, D):
+    """(splits, chunk, workspace_bytes) of fa2_decode for this shape; depends on nothing else. C entry cln_fa2_decode_plan."""
+    from . import host
+    return host.fa2_decode_plan(B, H, Nmax, D)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

@@ -2,7 +2,7 @@
 //
 //   int cln_describe(const char* name, int d0, int d1, int d2, int d3, int stages, char* buf, int buflen)
 //     HGEMM names (G6 signature) and the two sgemm matrix-core names (S6):  d0 = M, d1 = N, d2 = K, d3 unused
-//     flash-attn names:            d0 = B, d1 = H, d2 = N, d3 = D   (the cln_fa2_* names of include/cln_amd_ext.h too)
+//     flash-attn names:            d0 = B, d1 = H, d2 = N, d3 = D   (the cln_fa2_* names of include/cln_amd_ext.h too; cln_fa2_decode: d2 = Nmax)
 //   returns the length of the text written to buf (NUL-terminated), or
 //     CLN_ERR_UNSUPPORTED (-2)  the name exists but the shape is outside its supported set (the launch would fail too)
 //     CLN_ERR_BAD_ARG (-1)      not a run-time dispatched name: one fixed kernel, named in manifest.py `impl`
@@ -18,6 +18,7 @@ int cln_sgemm_describe(const char* name, int M, int N, int K, int stages, char* 
 int cln_fa_causal_describe(const char* name, int B, int H, int N, int D, int stages, char* buf, int len);  // flash_attn_causal.hip (cln_amd_ext.h)
 int cln_fa_lse_describe(const char* name, int B, int H, int N, int D, int stages, char* buf, int len);     // flash_attn_fwd_lse.hip (cln_amd_ext.h)
 int cln_fa_bwd_describe(const char* name, int B, int H, int N, int D, int stages, char* buf, int len);     // flash_attn_bwd.hip (cln_amd_ext.h)
+int cln_fa_decode_describe(const char* name, int B, int H, int Nmax, int D, int stages, char* buf, int len);  // flash_attn_decode.hip (cln_amd_ext.h)
 
 CLN_API int cln_describe(const char* name, int d0, int d1, int d2, int d3, int stages, char* buf, int buflen) {
   if (!name || !buf || buflen <= 0) return CLN_ERR_BAD_ARG;
@@ -28,6 +29,8 @@ CLN_API int cln_describe(const char* name, int d0, int d1, int d2, int d3, int s
   rc = cln_fa_lse_describe(name, d0, d1, d2, d3, stages, buf, buflen);
   if (rc != CLN_ERR_BAD_ARG) return rc;
   rc = cln_fa_bwd_describe(name, d0, d1, d2, d3, stages, buf, buflen);
+  if (rc != CLN_ERR_BAD_ARG) return rc;
+  rc = cln_fa_decode_describe(name, d0, d1, d2, d3, stages, buf, buflen);
   if (rc != CLN_ERR_BAD_ARG) return rc;
   rc = cln_sgemm_describe(name, d0, d1, d2, stages, buf, buflen);
   if (rc != CLN_ERR_BAD_ARG) return rc;

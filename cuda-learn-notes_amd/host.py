@@ -673,3 +673,51 @@ def fa2_bwd(Q, K, V, O, dO, LSE, dQ, dK, dV, delta=None, causal=False):
     rc = fn(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), LSE.data_ptr(), delta.data_ptr(),
             dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), B, H, N, D, _stream())
     _check_bh("fa2_bwd", B, H, N, D, rc)
+
+
+def fa2_decode_plan(B, H, Nmax, D):
+    """(splits, chunk, workspace_bytes) of fa2_decode for caches of fp16 [B,H,Nmax,D]: a function of these four numbers only
+    (cln_fa2_decode_plan, include/cln_amd_ext.h). No GPU needed."""
+    fn = _ext_fn("cln_fa2_decode_plan", [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3)
+    s, c, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
+    rc = fn(int(B), int(H), int(Nmax), int(D), ctypes.addressof(s), ctypes.addressof(c), ctypes.addressof(w))
+    if rc == -2 and D not in (64, 128):
+        raise RuntimeError("fa2_decode: headdim %d not supported (64 or 128)" % D)
+    _raise("fa2_decode", rc, "fa2_decode: B * H * splits = too many workgroups for one launch")
+    return s.value, c.value, w.value
+
+
+def fa2_decode(q, k_cache, v_cache, seqlens, out, lse=None, workspace=None):
+    """Single-query attention over a KV cache into out: q, out fp16 [B,H,D], k_cache, v_cache fp16 [B,H,Nmax,D], seqlens int32 [B] on the GPU
+    (clamped to [0, Nmax] by the kernels, never read by the host), lse fp32 [B,H] (natural log) or None; D in {64, 128}. workspace: any
+    contiguous GPU tensor of at least fa2_decode_plan(...)[2] bytes; allocated here on the current stream when None and the plan splits the
+    keys. Deterministic. C entry cln_fa2_decode (include/cln_amd_ext.h); no CPU path."""
+    fn = _ext_fn("cln_fa2_decode", [ctypes.c_void_p] * 7 + [ctypes.c_longlong] + [ctypes.c_int] * 4 + [ctypes.c_void_p])
+    for t in (q, k_cache, v_cache, out):
+        _check_dtype(t, torch.float16)
+    _check_dtype(seqlens, torch.int32)
+    _check_dev(q, k_cache, v_cache, seqlens, out)
+    if q.dim() != 3 or k_cache.dim() != 4:
+        raise RuntimeError("Tensor size mismatch!")
+    B, H, D = q.shape
+    Nmax = k_cache.shape[2]
+    _check_shape(k_cache, B, H, Nmax, D)
+    _check_shape(v_cache, B, H, Nmax, D)
+    _check_shape(out, B, H, D)
+    _check_shape(seqlens, B)
+    if lse is not None:
+        _check_dtype(lse, torch.float32)
+        _check_dev(lse)
+        _check_shape(lse, B, H)
+    need = fa2_decode_plan(B, H, Nmax, D)[2]
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ws_ptr, ws_bytes = None, 0
+    if workspace is not None:
+        _check_dev(workspace)
+        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+        if ws_bytes < need:
+            raise RuntimeError("fa2_decode: workspace of %d bytes, the plan needs %d (fa2_decode_plan)" % (ws_bytes, need))
+    rc = fn(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), seqlens.data_ptr(), out.data_ptr(), None if lse is None else lse.data_ptr(),
+            ws_ptr, ws_bytes, B, H, Nmax, D, _stream())
+    _raise("fa2_decode", rc)

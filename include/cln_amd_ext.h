@@ -38,6 +38,22 @@ int cln_fa2_bwd(const void* q, const void* k, const void* v, const void* o, cons
 int cln_fa2_bwd_causal(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, float* delta,
                        void* dq, void* dk, void* dv, int B, int H, int N, int D, void* stream);
 
+/* ---- Single-query ("decode") attention over a KV cache: O[b,h,:] = sum_{j < len_b} softmax_j(q . K_j / sqrt(D)) V_j.
+ * q, o: fp16 [B,H,D]; k_cache, v_cache: fp16 [B,H,Nmax,D] contiguous; seqlens: int32 [B] ON THE DEVICE (the host never reads it: no sync, the call can
+ * be captured in a graph); lse: fp32 [B,H] (natural log) or NULL. The kernels clamp each length to [0, Nmax]; a clamped length of 0 gives O = 0 and
+ * LSE = -inf. No cache row at index >= min(len_b, Nmax) is read. Supported: D in {64, 128}; Nmax is any positive number.
+ * cln_fa2_decode_plan: the split of the keys this (B, H, Nmax, D) runs with -- *splits chunks of *chunk keys per head -- and the bytes of workspace
+ * the call needs: B H splits (D + 2) 4 when splits > 1, else 0 (a NULL workspace is then accepted). The plan depends on nothing else, so the bits of
+ * a sequence do not depend on the lengths of its neighbours. The library allocates nothing; results are bit-repeatable (no atomics).
+ * Returns 0, -1 (null q / k_cache / v_cache / seqlens / o; a q, k_cache, v_cache, o, lse or workspace pointer that is not 16-byte aligned or a seqlens
+ * pointer that is not 4-byte aligned; non-positive B, H, Nmax or D; o, lse or workspace equal to an input or to each other; splits > 1 with a NULL
+ * workspace or workspace_bytes below the plan's), -2 (other D, grid too large) -- all checked before any device access -- or -3 (launch error).
+ * cln_describe("cln_fa2_decode", B, H, Nmax, D, stages, ...) names the kernels and the plan; the stages argument is ignored.
+ */
+int cln_fa2_decode_plan(int B, int H, int Nmax, int D, int* splits, int* chunk, long long* workspace_bytes);
+int cln_fa2_decode(const void* q, const void* k_cache, const void* v_cache, const int* seqlens, void* o, float* lse,
+                   void* workspace, long long workspace_bytes, int B, int H, int Nmax, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
