@@ -54,6 +54,34 @@ int cln_fa2_decode_plan(int B, int H, int Nmax, int D, int* splits, int* chunk, 
 int cln_fa2_decode(const void* q, const void* k_cache, const void* v_cache, const int* seqlens, void* o, float* lse,
                    void* workspace, long long workspace_bytes, int B, int H, int Nmax, int D, void* stream);
 
+/* ---- Decode attention over a PAGED KV cache with grouped query heads (GQA / MQA):
+ *   O[b,h,:] = sum_{j < len_b} softmax_j(q[b,h] . K_j / sqrt(D)) V_j, where key j of sequence b and query head h is row j % page of KV head h / G in
+ *   the physical page block_table[b, j / page], G = Hq / Hkv.
+ * q, o: fp16 [B,Hq,D]; k_pages, v_pages: fp16 [P,Hkv,page,D] contiguous (one pool of P pages, the rows of one head in one page consecutive);
+ * block_table: int32 [B,max_pages] and seqlens: int32 [B], both ON THE DEVICE (the host reads neither: no sync, the call can be captured in a graph
+ * and replayed after the table, the lengths and the cache have changed); lse: fp32 [B,Hq] (natural log) or NULL.
+ * Supported: D in {64, 128}; Hq = G Hkv with G in {1, 2, 4, 8}; page in {16, 32, 64, 128, 256}; any P >= 1 and max_pages >= 1 with
+ * max_pages page < 2^31. The kernels clamp each length to [0, max_pages page]; a clamped length of 0 gives O = 0 and LSE = -inf.
+ * Of a sequence only the table entries 0 .. ceil(len_b / page) - 1 are read, and only the rows < len_b of the pages they name: entries past that and
+ * pool pages that no live entry names may hold anything. THE LIVE ENTRIES MUST LIE IN [0, P): the kernels do not check them -- that is the caller's
+ * contract, like the pointers (P itself is only checked to be positive). One workgroup serves all G query heads of a KV head, so every K and V row is
+ * read once per KV head.
+ * cln_fa2_decode_paged_plan: the split this (B, Hq, Hkv, max_pages, page, D) runs with -- *splits chunks of *chunk keys (a multiple of the page) --
+ * and the bytes of workspace the call needs: B Hq splits (D + 2) 4 when splits > 1, else 0 (a NULL workspace is then accepted). The plan depends on
+ * nothing else, so the bits of a sequence depend neither on its neighbours nor on where its pages lie. The library allocates nothing; results are
+ * bit-repeatable (no atomics).
+ * Returns 0, -1 (null q / k_pages / v_pages / block_table / seqlens / o; a q, k_pages, v_pages, o, lse or workspace pointer that is not 16-byte
+ * aligned or a block_table / seqlens pointer that is not 4-byte aligned; non-positive B, Hq, Hkv, P, max_pages, page or D; Hq % Hkv != 0; o, lse or
+ * workspace equal to an input or to each other; splits > 1 with a NULL workspace or workspace_bytes below the plan's), -2 (other D, G or page,
+ * max_pages page >= 2^31, grid too large) -- all checked before any device access -- or -3 (launch error).
+ * cln_fa2_decode_paged_describe writes the kernel instantiations and the plan as text into buf (at most len bytes, NUL-terminated) and returns the
+ * text's length, or the same -1 / -2 (cln_describe carries four dims only, so this entry has its own).
+ */
+int cln_fa2_decode_paged_plan(int B, int Hq, int Hkv, int max_pages, int page, int D, int* splits, int* chunk, long long* workspace_bytes);
+int cln_fa2_decode_paged(const void* q, const void* k_pages, const void* v_pages, const int* block_table, const int* seqlens, void* o, float* lse,
+                         void* workspace, long long workspace_bytes, int B, int Hq, int Hkv, int P, int max_pages, int page, int D, void* stream);
+int cln_fa2_decode_paged_describe(int B, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
