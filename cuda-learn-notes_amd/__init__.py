@@ -73,6 +73,22 @@ def fa2_decode_paged_plan(B, Hq, Hkv, max_pages, page, D):
     return host.fa2_decode_paged_plan(B, Hq, Hkv, max_pages, page, D)
 
 
+def fa2_decode_paged_multi(q, k_pages, v_pages, block_table, seqlens, out, lse=None, workspace=None):
+    """Multi-token decode attention (speculative verify, short appends) over a paged KV cache with grouped query heads into out: q, out fp16
+    [B,T,Hq,D], k_pages / v_pages fp16 [P,Hkv,page,D], block_table int32 [B,max_pages] and seqlens int32 [B] on the GPU (the lengths count the T
+    newest tokens), lse fp32 [B,T,Hq] or None; query t sees the keys j < len - (T - 1 - t). T in 1 … 8, D in {64, 128}, Hq / Hkv in
+    {1, 2, 4, 8}, page in {16, ..., 256}. C entry cln_fa2_decode_paged_multi (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_decode_paged_multi(q, k_pages, v_pages, block_table, seqlens, out, lse, workspace)
+
+
+def fa2_decode_paged_multi_plan(B, T, Hq, Hkv, max_pages, page, D):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi for this shape; depends on nothing else. C entry
+    cln_fa2_decode_paged_multi_plan."""
+    from . import host
+    return host.fa2_decode_paged_multi_plan(B, T, Hq, Hkv, max_pages, page, D)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

@@ -791,3 +791,62 @@ def fa2_decode_paged(q, k_pages, v_pages, block_table, seqlens, out, lse=None, w
     rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), out.data_ptr(),
             None if lse is None else lse.data_ptr(), ws_ptr, ws_bytes, B, Hq, Hkv, P, max_pages, page, D, _stream())
     _raise("fa2_decode_paged", rc)
+
+
+def fa2_decode_paged_multi_plan(B, T, Hq, Hkv, max_pages, page, D):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi: a function of these seven numbers only (cln_fa2_decode_paged_multi_plan,
+    include/cln_amd_ext.h). No GPU needed."""
+    fn = _ext_fn("cln_fa2_decode_paged_multi_plan", [ctypes.c_int] * 7 + [ctypes.c_void_p] * 3)
+    s, c, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
+    args = (int(B), int(T), int(Hq), int(Hkv), int(max_pages), int(page), int(D))
+    rc = fn(*args, ctypes.addressof(s), ctypes.addressof(c), ctypes.addressof(w))
+    if rc == -2:
+        if args[6] in (64, 128) and args[1] > 8:
+            raise RuntimeError("fa2_decode_paged_multi: T %d not supported (1 … 8)" % args[1])
+        raise RuntimeError(str(_paged_unsupported(args[0], *args[2:])).replace("fa2_decode_paged:", "fa2_decode_paged_multi:"))
+    if rc == -1 and args[3] > 0 and args[2] % args[3]:
+        raise RuntimeError("fa2_decode_paged_multi: %d query heads are no multiple of %d KV heads" % (args[2], args[3]))
+    _raise("fa2_decode_paged_multi", rc)
+    return s.value, c.value, w.value
+
+
+def fa2_decode_paged_multi(q, k_pages, v_pages, block_table, seqlens, out, lse=None, workspace=None):
+    """Multi-token (speculative verify / short append) attention over a paged KV cache with grouped query heads into out: q, out fp16
+    [B,T,Hq,D]; k_pages, v_pages fp16 [P,Hkv,page,D]; block_table int32 [B,max_pages] and seqlens int32 [B] on the GPU (never read by the host;
+    lengths clamped to [0, max_pages * page] by the kernels; the live table entries must lie in [0, P)); lse fp32 [B,T,Hq] (natural log) or
+    None. seqlens[b] counts the T newest tokens, whose K / V rows are already in the pool; query t sees the keys j < len_b - (T - 1 - t), and
+    a query that sees none gets O = 0 and LSE = -inf. T in 1 … 8, D in {64, 128}, Hq / Hkv in {1, 2, 4, 8}, page in {16, 32, 64, 128, 256}.
+    workspace: any contiguous GPU tensor of at least fa2_decode_paged_multi_plan(...)[2] bytes; allocated here on the current stream when None
+    and the plan splits the keys. Deterministic. C entry cln_fa2_decode_paged_multi (include/cln_amd_ext.h); no CPU path."""
+    fn = _ext_fn("cln_fa2_decode_paged_multi", [ctypes.c_void_p] * 8 + [ctypes.c_longlong] + [ctypes.c_int] * 8 + [ctypes.c_void_p])
+    for t in (q, k_pages, v_pages, out):
+        _check_dtype(t, torch.float16)
+    _check_dtype(block_table, torch.int32)
+    _check_dtype(seqlens, torch.int32)
+    _check_dev(q, k_pages, v_pages, block_table, seqlens, out)
+    if q.dim() != 4 or k_pages.dim() != 4 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    B, T, Hq, D = q.shape
+    P, Hkv, page = k_pages.shape[:3]
+    max_pages = block_table.shape[1]
+    _check_shape(k_pages, P, Hkv, page, D)
+    _check_shape(v_pages, P, Hkv, page, D)
+    _check_shape(block_table, B, max_pages)
+    _check_shape(out, B, T, Hq, D)
+    _check_shape(seqlens, B)
+    if lse is not None:
+        _check_dtype(lse, torch.float32)
+        _check_dev(lse)
+        _check_shape(lse, B, T, Hq)
+    need = fa2_decode_paged_multi_plan(B, T, Hq, Hkv, max_pages, page, D)[2]
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ws_ptr, ws_bytes = None, 0
+    if workspace is not None:
+        _check_dev(workspace)
+        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+        if ws_bytes < need:
+            raise RuntimeError("fa2_decode_paged_multi: workspace of %d bytes, the plan needs %d (fa2_decode_paged_multi_plan)" % (ws_bytes, need))
+    rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), out.data_ptr(),
+            None if lse is None else lse.data_ptr(), ws_ptr, ws_bytes, B, T, Hq, Hkv, P, max_pages, page, D, _stream())
+    _raise("fa2_decode_paged_multi", rc)

@@ -82,6 +82,32 @@ int cln_fa2_decode_paged(const void* q, const void* k_pages, const void* v_pages
                          void* workspace, long long workspace_bytes, int B, int Hq, int Hkv, int P, int max_pages, int page, int D, void* stream);
 int cln_fa2_decode_paged_describe(int B, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len);
 
+/* ---- Multi-token decode attention (speculative verify, short chunked appends) over the same PAGED KV cache, on the matrix cores:
+ *   O[b,t,h,:] = sum_{j < n(b,t)} softmax_j(q[b,t,h] . K_j / sqrt(D)) V_j,  n(b,t) = len_b - (T - 1 - t),
+ *   keys through the block table exactly as for cln_fa2_decode_paged. len_b = clamp(seqlens[b], 0, max_pages page) counts the keys of sequence b
+ *   INCLUDING its T newest tokens, whose K / V rows the caller has already written: query t is the token at position len_b - T + t and sees itself
+ *   and everything before it. n(b,t) <= 0 (possible when len_b < T) gives O = 0 and LSE = -inf for that query.
+ * q, o: fp16 [B,T,Hq,D]; k_pages, v_pages: fp16 [P,Hkv,page,D]; block_table: int32 [B,max_pages] and seqlens: int32 [B], both ON THE DEVICE and never
+ * read by the host; lse: fp32 [B,T,Hq] (natural log) or NULL.
+ * Supported: T in 1 .. 8; D, G = Hq / Hkv, page, P and max_pages as for cln_fa2_decode_paged. Of a sequence only the table entries
+ * 0 .. ceil(len_b / page) - 1 are read, and only the rows < len_b of the pages they name; THE LIVE ENTRIES MUST LIE IN [0, P). One workgroup serves
+ * all T G query rows of a KV head, so every K and V row is read once per KV head and call, whatever T is.
+ * cln_fa2_decode_paged_multi_plan: the split this (B, T, Hq, Hkv, max_pages, page, D) runs with -- *splits chunks of *chunk keys (a multiple of
+ * max(page, 128)) -- and the bytes of workspace the call needs: B T Hq splits (D + 2) 4 when splits > 1, else 0 (a NULL workspace is then
+ * accepted). The plan depends on nothing else, so the bits of a sequence depend neither on its neighbours nor on where its pages lie. The library
+ * allocates nothing; results are bit-repeatable (no atomics).
+ * Returns 0, -1 (as cln_fa2_decode_paged, with T among the dimensions that must be positive), -2 (T > 8; other D, G or page; max_pages page >= 2^31;
+ * grid too large) -- all checked before any device access -- or -3 (launch error).
+ * cln_fa2_decode_paged_multi_describe writes the kernel instantiations and the plan as text into buf (at most len bytes, NUL-terminated) and returns
+ * the text's length, or the same -1 / -2.
+ */
+int cln_fa2_decode_paged_multi_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int* splits, int* chunk,
+                                    long long* workspace_bytes);
+int cln_fa2_decode_paged_multi(const void* q, const void* k_pages, const void* v_pages, const int* block_table, const int* seqlens, void* o,
+                               float* lse, void* workspace, long long workspace_bytes, int B, int T, int Hq, int Hkv, int P, int max_pages, int page,
+                               int D, void* stream);
+int cln_fa2_decode_paged_multi_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
