@@ -16,31 +16,27 @@
 //                 k-slots of a lane: the dataflow of flash_attn_m16x, tests/test_fragment_layout_model.py), A = V^T fragments through a
 //                 wave-private LDS image of the 32 V rows and ds_read_b64_tr_b16. V rows travel global -> registers (the same addresses as the K
 //                 rows: one table lookup serves both) -> LDS; rows at or past len_b are NOT loaded and stored as zeros (0 x NaN = NaN in an MFMA).
-// The table entries of step i + 2 are fetched while the rows of step i + 1 are in flight (the lookahead of fa2p::). The LDS image belongs to one
+// The table entries of step i + 2 are fetched while the rows of step i + 1 are in flight (fa2d::PagedKV). The LDS image belongs to one
 // wave: LDS instructions of a wave execute in order, so a compiler barrier is all the write -> transposed read -> next write chain needs.
 // At the end the four waves merge per row tile through LDS (which reuses the V images) in a fixed order; with S > 1 the workgroup writes
-// unnormalised fp32 partials of all its R rows -- (-inf, 0, 0) for a row that saw no key of this split -- and fa2_decode_paged_multi_combine_kernel
-// merges the live splits ceil(len_b / C) of a row in ascending s with the -inf guard. No atomics.
-//
-// Workspace layout (floats): O partials [B T Hq][S][D], then (m, l) pairs [B T Hq][S][2]  ->  B T Hq S (D + 2) 4 bytes.
+// unnormalised fp32 partials of all its R rows -- (-inf, 0, 0) for a row that saw no key of this split -- and fa2d::fa2_decode_combine_kernel
+// merges the live splits ceil(len_b / C) of a row in ascending s with the -inf guard (flash_attn_decode_common.cuh, which also has the workspace
+// layout: its rows are the B T Hq query rows). No atomics.
 #pragma once
-#include "flash_attn_decode.cuh"
+#include "flash_attn_decode_common.cuh"
 
 namespace fa2pm {
 
-constexpr int kWaves = 4;
-constexpr int kThreads = kWaves * CLN_WAVE;
+using fa2d::kThreads;
+using fa2d::kWaves;
 constexpr int kWaveKeys = 32;                  // keys of one wave in one step: two 16-key S^T blocks = the 32 k-slots of one P V MFMA
 constexpr int kKeyStep = kWaves * kWaveKeys;  // keys per workgroup step, for both head dims
 constexpr int kMaxT = 8;
 
 template <int D, int MT>
-__global__ __launch_bounds__(kThreads) void fa2_decode_paged_multi_kernel(const half_t* __restrict__ q, const half_t* __restrict__ kp,
-                                                                          const half_t* __restrict__ vp, const int* __restrict__ block_table,
-                                                                          const int* __restrict__ seqlens, half_t* __restrict__ o,
-                                                                          float* __restrict__ lse, float* __restrict__ ws_o, float* __restrict__ ws_ml,
-                                                                          int T, int Hkv, int g_shift, int max_pages, int page_shift, int S, int C,
-                                                                          float scale_log2) {
+__global__ __launch_bounds__(kThreads) void fa2_decode_paged_multi_kernel(const half_t* __restrict__ q, const fa2d::PagedKV kv,
+                                                                          const int* __restrict__ seqlens, const fa2d::Out out, int T, int g_shift,
+                                                                          int S, int C, float scale_log2) {
   static_assert(D == 64 || D == 128, "head dim");
   static_assert(MT >= 1 && MT <= 4, "row tiles");
   constexpr int KS = D / 32;         // k-steps of S^T
@@ -51,20 +47,15 @@ __global__ __launch_bounds__(kThreads) void fa2_decode_paged_multi_kernel(const 
   constexpr int M_BYTES = kWaves * 16 * (OROW + 2) * 4;
   __shared__ __attribute__((aligned(16))) unsigned char smem[V_BYTES > M_BYTES ? V_BYTES : M_BYTES];
 
-  const unsigned bk = blockIdx.x / (unsigned)S, s = blockIdx.x - bk * (unsigned)S;  // bk = b Hkv + KV head
-  const unsigned b = bk / (unsigned)Hkv, kvh = bk - b * (unsigned)Hkv;
-  const int Nmax = max_pages << page_shift;  // the plan checked that it fits
-  const int len = min(max(seqlens[b], 0), Nmax);
-  const int lo = (int)s * C;  // (S - 1) C < Nmax: no overflow
-  if (S > 1 && lo >= len) return;  // a split wholly past the length: the combine kernel skips it by the same arithmetic
-  const unsigned n = len > lo ? (unsigned)min(C, len - lo) : 0u;  // keys of this workgroup: logical rows lo .. lo + n - 1
-
+  fa2d::Split sp;
+  if (!fa2d::split_of(sp, seqlens, kv.heads(), kv.nmax(), S, C)) return;
+  const unsigned n = sp.n;
+  const int len = sp.len, lo = sp.lo;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int i16 = lane & 15, g4 = lane >> 4;
-  const int G = 1 << g_shift, R = T << g_shift, Hq = Hkv << g_shift;
-  const int* bt = block_table + (size_t)b * max_pages;
-  const unsigned off_mask = (1u << page_shift) - 1u;
-  const size_t row_bt = (size_t)b * T * Hq + (size_t)kvh * G;  // output row of (t, g): row_bt + t Hq + g
+  const fa2d::PagedKV::At at = kv.at(sp, D, 8 * g4);
+  const int G = 1 << g_shift, R = T << g_shift, Hq = kv.Hkv << g_shift;
+  const size_t row_bt = (size_t)sp.b * T * Hq + (size_t)sp.h * G;  // output row of (t, g): row_bt + t Hq + g
 
   // the query fragments and, per row tile, the number of keys OF THIS SPLIT the lane's query sees (<= 0: none)
   h8 qf[MT][KS];
@@ -86,13 +77,10 @@ __global__ __launch_bounds__(kThreads) void fa2_decode_paged_multi_kernel(const 
   struct Rows {
     h8 k[2][KS], v[2][KS];
   };
-  // the physical pages of this lane's two rows of the step at r0; rows at or past n have no table entry that is ours to read
+  // the physical pages of this lane's two rows of the step at r0
   auto lookup = [&](int (&pg)[2], unsigned r0) {
 #pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      const unsigned r = r0 + row0 + 16 * kb;
-      pg[kb] = r < n ? bt[((unsigned)lo + r) >> page_shift] : 0;
-    }
+    for (int kb = 0; kb < 2; ++kb) pg[kb] = kv.lookup(at, r0 + row0 + 16 * kb, n);
   };
   // rows at or past n are not addressed at all: their K and V fragments are zero
   auto load = [&](Rows& d, const int (&pg)[2], unsigned r0) {
@@ -102,11 +90,11 @@ __global__ __launch_bounds__(kThreads) void fa2_decode_paged_multi_kernel(const 
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) d.k[kb][ks] = h8{0, 0, 0, 0, 0, 0, 0, 0}, d.v[kb][ks] = h8{0, 0, 0, 0, 0, 0, 0, 0};
       if (r < n) {
-        const size_t e = (((((size_t)pg[kb] * Hkv + kvh) << page_shift) + (((unsigned)lo + r) & off_mask)) * D) + 8 * g4;
+        const size_t e = kv.elem(at, pg[kb], r, D);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-          d.k[kb][ks] = *reinterpret_cast<const h8*>(kp + e + 32 * ks);
-          d.v[kb][ks] = *reinterpret_cast<const h8*>(vp + e + 32 * ks);
+          d.k[kb][ks] = *reinterpret_cast<const h8*>(at.k + e + 32 * ks);
+          d.v[kb][ks] = *reinterpret_cast<const h8*>(at.v + e + 32 * ks);
         }
       }
     }
@@ -215,83 +203,25 @@ __global__ __launch_bounds__(kThreads) void fa2_decode_paged_multi_kernel(const 
       const int qi = idx / D, d = idx % D;
       const int r = 16 * qb + qi;
       if (r < R) {
-        float mx = sm_ml[qi * 2];
-#pragma unroll
-        for (int i = 1; i < kWaves; ++i) mx = fmaxf(mx, sm_ml[(i * 16 + qi) * 2]);
-        const float ms = mx == FA2D_NEG_INF ? 0.0f : mx;
-        float L = 0.0f, O = 0.0f;
-#pragma unroll
-        for (int i = 0; i < kWaves; ++i) {
-          const float f = fa2d::ex2(sm_ml[(i * 16 + qi) * 2] - ms);
-          L += sm_ml[(i * 16 + qi) * 2 + 1] * f;
-          O += sm_o[(i * 16 + qi) * OROW + d] * f;
-        }
-        const size_t row = row_bt + (size_t)(r >> g_shift) * Hq + (r & (G - 1));
-        if (S == 1) {
-          const float inv = L > 0.0f ? 1.0f / L : 0.0f;  // no visible key: O = 0, LSE = -inf
-          o[row * D + d] = (half_t)(O * inv);
-          if (lse && d == 0) lse[row] = L > 0.0f ? (mx + __builtin_log2f(L)) * 0.6931471805599453f : FA2D_NEG_INF;
-        } else {
-          const size_t cell = row * S + s;
-          ws_o[cell * D + d] = O;
-          if (d == 0) ws_ml[cell * 2] = mx, ws_ml[cell * 2 + 1] = L;
-        }
+        float mx, L, O;
+        fa2d::reduce_waves(sm_ml + qi * 2, 16 * 2, sm_o + qi * OROW + d, 16 * OROW, mx, L, O);
+        fa2d::store_split<D>(out, row_bt + (size_t)(r >> g_shift) * Hq + (r & (G - 1)), d, sp.s, S, mx, L, O);
       }
     }
     if (qb + 1 < MT) __syncthreads();
   }
 }
 
-// One workgroup of D threads per query row (b, t, h): the live splits ceil(len_b / C) of its sequence, merged in ascending s. A live split may hold
-// no key this row sees (its partial is (-inf, 0, 0)), and a row with n(b,t) <= 0 sees none at all: the maximum may be -inf.
-template <int D>
-__global__ __launch_bounds__(D) void fa2_decode_paged_multi_combine_kernel(const float* __restrict__ ws_o, const float* __restrict__ ws_ml,
-                                                                           const int* __restrict__ seqlens, half_t* __restrict__ o,
-                                                                           float* __restrict__ lse, int THq, int Nmax, int S, int C) {
-  const unsigned row = blockIdx.x;
-  const int d = threadIdx.x;
-  const unsigned len = (unsigned)min(max(seqlens[row / (unsigned)THq], 0), Nmax);
-  const int live = (int)((len + (unsigned)C - 1u) / (unsigned)C);  // <= S, as S C >= Nmax
-  const float* ml = ws_ml + (size_t)row * S * 2;
-  const float* po = ws_o + (size_t)row * S * D + d;
-  float mx = FA2D_NEG_INF;
-  for (int s = 0; s < live; ++s) mx = fmaxf(mx, ml[2 * s]);
-  const float ms = mx == FA2D_NEG_INF ? 0.0f : mx;  // never exp2(-inf + inf)
-  float L = 0.0f, O = 0.0f;
-  for (int s = 0; s < live; ++s) {
-    const float f = fa2d::ex2(ml[2 * s] - ms);
-    L += ml[2 * s + 1] * f;
-    O += po[(size_t)s * D] * f;
-  }
-  const float inv = L > 0.0f ? 1.0f / L : 0.0f;
-  o[(size_t)row * D + d] = (half_t)(O * inv);
-  if (lse && d == 0) lse[row] = L > 0.0f ? (mx + __builtin_log2f(L)) * 0.6931471805599453f : FA2D_NEG_INF;
-}
-
-inline long long workspace_bytes(int B, int T, int Hq, int S, int D) { return S > 1 ? (long long)B * T * Hq * S * (D + 2) * 4 : 0; }
-
-// B Hkv S workgroups of 256 threads, then B T Hq workgroups of D threads, both in x; HIP takes at most 2^32 - 1 threads per grid dimension
-inline bool grid_fits(int B, int T, int Hq, int Hkv, int S, int D) {
-  return (long long)B * Hkv * S * kThreads <= 0xffffffffLL && (long long)B * T * Hq * D <= 0xffffffffLL;
-}
-
 // S splits of C keys (C a multiple of max(page, kKeyStep), S C >= max_pages page > (S - 1) C: the callers check it). No host read of the table or
 // the lengths, no allocation.
 template <int D, int MT>
-int launch_decode_paged_multi(const void* q, const void* kp, const void* vp, const int* block_table, const int* seqlens, void* o, float* lse,
-                              void* workspace, int B, int T, int Hkv, int g_shift, int max_pages, int page_shift, int S, int C, hipStream_t stream) {
-  const float scale_log2 = (float)(1.4426950408889634 / sqrt((double)D));
-  const int Hq = Hkv << g_shift;
-  float* ws_o = (float*)workspace;
-  float* ws_ml = S > 1 ? ws_o + (size_t)B * T * Hq * S * D : nullptr;
-  CLN_LAUNCH((fa2_decode_paged_multi_kernel<D, MT>), dim3((unsigned)((long long)B * Hkv * S)), dim3(kThreads), 0, stream, (const half_t*)q,
-             (const half_t*)kp, (const half_t*)vp, block_table, seqlens, (half_t*)o, lse, ws_o, ws_ml, T, Hkv, g_shift, max_pages, page_shift, S, C,
-             scale_log2);
-  int rc = cln_check_launch();
-  if (rc != CLN_OK || S == 1) return rc;
-  CLN_LAUNCH((fa2_decode_paged_multi_combine_kernel<D>), dim3((unsigned)(B * T * Hq)), dim3(D), 0, stream, (const float*)ws_o,
-             (const float*)ws_ml, seqlens, (half_t*)o, lse, T * Hq, max_pages << page_shift, S, C);
-  return cln_check_launch();
+int launch_decode_paged_multi(const void* q, const fa2d::PagedKV& kv, const int* seqlens, void* o, float* lse, void* workspace, int B, int T,
+                              int g_shift, int S, int C, hipStream_t stream) {
+  const long long bk = (long long)B * kv.Hkv, rows = (bk * T) << g_shift;
+  const fa2d::Out out = fa2d::make_out(o, lse, workspace, rows, S, D);
+  CLN_LAUNCH((fa2_decode_paged_multi_kernel<D, MT>), dim3((unsigned)(bk * S)), dim3(kThreads), 0, stream, (const half_t*)q, kv, seqlens, out, T,
+             g_shift, S, C, fa2d::scale_log2(D));
+  return fa2d::launch_combine<D>(cln_check_launch(), out, seqlens, rows, T * (kv.Hkv << g_shift), kv.nmax(), S, C, stream);
 }
 
 }  // namespace fa2pm

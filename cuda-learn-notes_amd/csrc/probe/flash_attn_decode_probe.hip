@@ -9,9 +9,10 @@ CLN_API int cln_fa2_decode_variant(const void* q, const void* k_cache, const voi
   if (!q || !k_cache || !v_cache || !seqlens || !o || B <= 0 || H <= 0 || Nmax <= 0) return CLN_ERR_BAD_ARG;
   if (D != 64 && D != 128) return CLN_ERR_UNSUPPORTED;
   if (S <= 0 || C <= 0 || C % fa2d::key_step(D) != 0 || (long long)S * C < Nmax || (long long)(S - 1) * C >= Nmax) return CLN_ERR_UNSUPPORTED;
-  if ((long long)B * H > 0x7fffffffLL || !fa2d::grid_fits(B, H, S)) return CLN_ERR_UNSUPPORTED;
-  if (S > 1 && (!workspace || workspace_bytes < fa2d::workspace_bytes(B, H, S, D))) return CLN_ERR_BAD_ARG;
+  if ((long long)B * H > 0x7fffffffLL || !fa2d::grid_fits((long long)B * H * S, (long long)B * H, D)) return CLN_ERR_UNSUPPORTED;
+  if (S > 1 && (!workspace || workspace_bytes < fa2d::workspace_bytes((long long)B * H, S, D))) return CLN_ERR_BAD_ARG;
   const hipStream_t s = (hipStream_t)stream;
-  if (D == 64) return fa2d::launch_decode<64>(q, k_cache, v_cache, seqlens, o, lse, workspace, B, H, Nmax, S, C, s);
-  return fa2d::launch_decode<128>(q, k_cache, v_cache, seqlens, o, lse, workspace, B, H, Nmax, S, C, s);
+  const fa2d::DenseKV kv = {(const half_t*)k_cache, (const half_t*)v_cache, H, Nmax};
+  if (D == 64) return fa2d::launch_decode<64, 1>(q, kv, seqlens, o, lse, workspace, B, S, C, s);
+  return fa2d::launch_decode<128, 1>(q, kv, seqlens, o, lse, workspace, B, S, C, s);
 }

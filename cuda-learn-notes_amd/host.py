@@ -675,16 +675,54 @@ def fa2_bwd(Q, K, V, O, dO, LSE, dQ, dK, dV, delta=None, causal=False):
     _check_bh("fa2_bwd", B, H, N, D, rc)
 
 
+def _decode_plan(cname, dims):
+    """(rc, (splits, chunk, workspace_bytes)) of a cln_fa2_decode*_plan entry for the int tuple dims."""
+    fn = _ext_fn(cname, [ctypes.c_int] * len(dims) + [ctypes.c_void_p] * 3)
+    s, c, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
+    rc = fn(*dims, ctypes.addressof(s), ctypes.addressof(c), ctypes.addressof(w))
+    return rc, (s.value, c.value, w.value)
+
+
+def _decode_check(f16, i32):
+    """The dtype and device checks the decode entries share: fp16 tensors, int32 tensors, all on the GPU."""
+    for t in f16:
+        _check_dtype(t, torch.float16)
+    for t in i32:
+        _check_dtype(t, torch.int32)
+    _check_dev(*f16, *i32)
+
+
+def _decode_lse(lse, *shape):
+    """The pointer of the optional fp32 lse of that shape."""
+    if lse is None:
+        return None
+    _check_dtype(lse, torch.float32)
+    _check_dev(lse)
+    _check_shape(lse, *shape)
+    return lse.data_ptr()
+
+
+def _decode_workspace(name, need, workspace, device):
+    """(pointer, bytes) of the workspace of entry `name`, whose plan needs `need` bytes: allocated here when None and the plan splits the keys."""
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+    if workspace is None:
+        return None, 0
+    _check_dev(workspace)
+    ws_bytes = workspace.numel() * workspace.element_size()
+    if ws_bytes < need:
+        raise RuntimeError("%s: workspace of %d bytes, the plan needs %d (%s_plan)" % (name, ws_bytes, need, name))
+    return workspace.data_ptr(), ws_bytes
+
+
 def fa2_decode_plan(B, H, Nmax, D):
     """(splits, chunk, workspace_bytes) of fa2_decode for caches of fp16 [B,H,Nmax,D]: a function of these four numbers only
     (cln_fa2_decode_plan, include/cln_amd_ext.h). No GPU needed."""
-    fn = _ext_fn("cln_fa2_decode_plan", [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3)
-    s, c, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
-    rc = fn(int(B), int(H), int(Nmax), int(D), ctypes.addressof(s), ctypes.addressof(c), ctypes.addressof(w))
+    rc, plan = _decode_plan("cln_fa2_decode_plan", (int(B), int(H), int(Nmax), int(D)))
     if rc == -2 and D not in (64, 128):
         raise RuntimeError("fa2_decode: headdim %d not supported (64 or 128)" % D)
     _raise("fa2_decode", rc, "fa2_decode: B * H * splits = too many workgroups for one launch")
-    return s.value, c.value, w.value
+    return plan
 
 
 def fa2_decode(q, k_cache, v_cache, seqlens, out, lse=None, workspace=None):
@@ -693,10 +731,7 @@ def fa2_decode(q, k_cache, v_cache, seqlens, out, lse=None, workspace=None):
     contiguous GPU tensor of at least fa2_decode_plan(...)[2] bytes; allocated here on the current stream when None and the plan splits the
     keys. Deterministic. C entry cln_fa2_decode (include/cln_amd_ext.h); no CPU path."""
     fn = _ext_fn("cln_fa2_decode", [ctypes.c_void_p] * 7 + [ctypes.c_longlong] + [ctypes.c_int] * 4 + [ctypes.c_void_p])
-    for t in (q, k_cache, v_cache, out):
-        _check_dtype(t, torch.float16)
-    _check_dtype(seqlens, torch.int32)
-    _check_dev(q, k_cache, v_cache, seqlens, out)
+    _decode_check((q, k_cache, v_cache, out), (seqlens,))
     if q.dim() != 3 or k_cache.dim() != 4:
         raise RuntimeError("Tensor size mismatch!")
     B, H, D = q.shape
@@ -705,51 +740,59 @@ def fa2_decode(q, k_cache, v_cache, seqlens, out, lse=None, workspace=None):
     _check_shape(v_cache, B, H, Nmax, D)
     _check_shape(out, B, H, D)
     _check_shape(seqlens, B)
-    if lse is not None:
-        _check_dtype(lse, torch.float32)
-        _check_dev(lse)
-        _check_shape(lse, B, H)
-    need = fa2_decode_plan(B, H, Nmax, D)[2]
-    if workspace is None and need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
-    ws_ptr, ws_bytes = None, 0
-    if workspace is not None:
-        _check_dev(workspace)
-        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-        if ws_bytes < need:
-            raise RuntimeError("fa2_decode: workspace of %d bytes, the plan needs %d (fa2_decode_plan)" % (ws_bytes, need))
-    rc = fn(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), seqlens.data_ptr(), out.data_ptr(), None if lse is None else lse.data_ptr(),
-            ws_ptr, ws_bytes, B, H, Nmax, D, _stream())
+    lse_ptr = _decode_lse(lse, B, H)
+    ws_ptr, ws_bytes = _decode_workspace("fa2_decode", fa2_decode_plan(B, H, Nmax, D)[2], workspace, q.device)
+    rc = fn(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), seqlens.data_ptr(), out.data_ptr(), lse_ptr, ws_ptr, ws_bytes, B, H, Nmax, D,
+            _stream())
     _raise("fa2_decode", rc)
 
 
 _PAGED_GROUPS, _PAGED_PAGES = (1, 2, 4, 8), (16, 32, 64, 128, 256)
 
 
-def _paged_unsupported(B, Hq, Hkv, max_pages, page, D):
-    """The RuntimeError for status -2 of the paged decode entries."""
+def _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D):
+    """The RuntimeError for status -2 of the paged decode entry `name`."""
     if D not in (64, 128):
-        return RuntimeError("fa2_decode_paged: headdim %d not supported (64 or 128)" % D)
+        return RuntimeError("%s: headdim %d not supported (64 or 128)" % (name, D))
     if Hkv > 0 and Hq % Hkv == 0 and Hq // Hkv not in _PAGED_GROUPS:
-        return RuntimeError("fa2_decode_paged: group size %d (= Hq %d / Hkv %d) not supported (1, 2, 4 or 8)" % (Hq // Hkv, Hq, Hkv))
+        return RuntimeError("%s: group size %d (= Hq %d / Hkv %d) not supported (1, 2, 4 or 8)" % (name, Hq // Hkv, Hq, Hkv))
     if page not in _PAGED_PAGES:
-        return RuntimeError("fa2_decode_paged: page size %d not supported (16, 32, 64, 128 or 256)" % page)
-    return RuntimeError("fa2_decode_paged: max_pages * page or B * Hkv * splits too large for one launch")
+        return RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+    return RuntimeError("%s: max_pages * page or B * Hkv * splits too large for one launch" % name)
+
+
+def _paged_decode(name, plan, q_dims, q, k_pages, v_pages, block_table, seqlens, out, lse, workspace):
+    """The body of fa2_decode_paged (q, out [B,Hq,D]) and fa2_decode_paged_multi ([B,T,Hq,D]): q_dims = 3 or 4, plan = the entry's *_plan."""
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 8 + [ctypes.c_longlong] + [ctypes.c_int] * (q_dims + 4) + [ctypes.c_void_p])
+    _decode_check((q, k_pages, v_pages, out), (block_table, seqlens))
+    if q.dim() != q_dims or k_pages.dim() != 4 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    lead, D = tuple(q.shape[:-1]), q.shape[-1]  # (B, Hq) or (B, T, Hq)
+    P, Hkv, page = k_pages.shape[:3]
+    max_pages = block_table.shape[1]
+    _check_shape(k_pages, P, Hkv, page, D)
+    _check_shape(v_pages, P, Hkv, page, D)
+    _check_shape(block_table, lead[0], max_pages)
+    _check_shape(out, *q.shape)
+    _check_shape(seqlens, lead[0])
+    lse_ptr = _decode_lse(lse, *lead)
+    ws_ptr, ws_bytes = _decode_workspace(name, plan(*lead, Hkv, max_pages, page, D)[2], workspace, q.device)
+    rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), out.data_ptr(), lse_ptr, ws_ptr,
+            ws_bytes, *lead, Hkv, P, max_pages, page, D, _stream())
+    _raise(name, rc)
 
 
 def fa2_decode_paged_plan(B, Hq, Hkv, max_pages, page, D):
     """(splits, chunk, workspace_bytes) of fa2_decode_paged: a function of these six numbers only (cln_fa2_decode_paged_plan,
     include/cln_amd_ext.h). No GPU needed."""
-    fn = _ext_fn("cln_fa2_decode_paged_plan", [ctypes.c_int] * 6 + [ctypes.c_void_p] * 3)
-    s, c, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
     args = (int(B), int(Hq), int(Hkv), int(max_pages), int(page), int(D))
-    rc = fn(*args, ctypes.addressof(s), ctypes.addressof(c), ctypes.addressof(w))
+    rc, plan = _decode_plan("cln_fa2_decode_paged_plan", args)
     if rc == -2:
-        raise _paged_unsupported(*args)
+        raise _paged_unsupported("fa2_decode_paged", *args)
     if rc == -1 and args[2] > 0 and args[1] % args[2]:
         raise RuntimeError("fa2_decode_paged: %d query heads are no multiple of %d KV heads" % (args[1], args[2]))
     _raise("fa2_decode_paged", rc)
-    return s.value, c.value, w.value
+    return plan
 
 
 def fa2_decode_paged(q, k_pages, v_pages, block_table, seqlens, out, lse=None, workspace=None):
@@ -759,55 +802,22 @@ def fa2_decode_paged(q, k_pages, v_pages, block_table, seqlens, out, lse=None, w
     Hq / Hkv in {1, 2, 4, 8}, page in {16, 32, 64, 128, 256}. workspace: any contiguous GPU tensor of at least fa2_decode_paged_plan(...)[2]
     bytes; allocated here on the current stream when None and the plan splits the keys. Deterministic. C entry cln_fa2_decode_paged
     (include/cln_amd_ext.h); no CPU path."""
-    fn = _ext_fn("cln_fa2_decode_paged", [ctypes.c_void_p] * 8 + [ctypes.c_longlong] + [ctypes.c_int] * 7 + [ctypes.c_void_p])
-    for t in (q, k_pages, v_pages, out):
-        _check_dtype(t, torch.float16)
-    _check_dtype(block_table, torch.int32)
-    _check_dtype(seqlens, torch.int32)
-    _check_dev(q, k_pages, v_pages, block_table, seqlens, out)
-    if q.dim() != 3 or k_pages.dim() != 4 or block_table.dim() != 2:
-        raise RuntimeError("Tensor size mismatch!")
-    B, Hq, D = q.shape
-    P, Hkv, page = k_pages.shape[:3]
-    max_pages = block_table.shape[1]
-    _check_shape(k_pages, P, Hkv, page, D)
-    _check_shape(v_pages, P, Hkv, page, D)
-    _check_shape(block_table, B, max_pages)
-    _check_shape(out, B, Hq, D)
-    _check_shape(seqlens, B)
-    if lse is not None:
-        _check_dtype(lse, torch.float32)
-        _check_dev(lse)
-        _check_shape(lse, B, Hq)
-    need = fa2_decode_paged_plan(B, Hq, Hkv, max_pages, page, D)[2]
-    if workspace is None and need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
-    ws_ptr, ws_bytes = None, 0
-    if workspace is not None:
-        _check_dev(workspace)
-        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-        if ws_bytes < need:
-            raise RuntimeError("fa2_decode_paged: workspace of %d bytes, the plan needs %d (fa2_decode_paged_plan)" % (ws_bytes, need))
-    rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), out.data_ptr(),
-            None if lse is None else lse.data_ptr(), ws_ptr, ws_bytes, B, Hq, Hkv, P, max_pages, page, D, _stream())
-    _raise("fa2_decode_paged", rc)
+    _paged_decode("fa2_decode_paged", fa2_decode_paged_plan, 3, q, k_pages, v_pages, block_table, seqlens, out, lse, workspace)
 
 
 def fa2_decode_paged_multi_plan(B, T, Hq, Hkv, max_pages, page, D):
     """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi: a function of these seven numbers only (cln_fa2_decode_paged_multi_plan,
     include/cln_amd_ext.h). No GPU needed."""
-    fn = _ext_fn("cln_fa2_decode_paged_multi_plan", [ctypes.c_int] * 7 + [ctypes.c_void_p] * 3)
-    s, c, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
     args = (int(B), int(T), int(Hq), int(Hkv), int(max_pages), int(page), int(D))
-    rc = fn(*args, ctypes.addressof(s), ctypes.addressof(c), ctypes.addressof(w))
+    rc, plan = _decode_plan("cln_fa2_decode_paged_multi_plan", args)
     if rc == -2:
         if args[6] in (64, 128) and args[1] > 8:
             raise RuntimeError("fa2_decode_paged_multi: T %d not supported (1 … 8)" % args[1])
-        raise RuntimeError(str(_paged_unsupported(args[0], *args[2:])).replace("fa2_decode_paged:", "fa2_decode_paged_multi:"))
+        raise _paged_unsupported("fa2_decode_paged_multi", args[0], *args[2:])
     if rc == -1 and args[3] > 0 and args[2] % args[3]:
         raise RuntimeError("fa2_decode_paged_multi: %d query heads are no multiple of %d KV heads" % (args[2], args[3]))
     _raise("fa2_decode_paged_multi", rc)
-    return s.value, c.value, w.value
+    return plan
 
 
 def fa2_decode_paged_multi(q, k_pages, v_pages, block_table, seqlens, out, lse=None, workspace=None):
@@ -818,35 +828,4 @@ def fa2_decode_paged_multi(q, k_pages, v_pages, block_table, seqlens, out, lse=N
     a query that sees none gets O = 0 and LSE = -inf. T in 1 … 8, D in {64, 128}, Hq / Hkv in {1, 2, 4, 8}, page in {16, 32, 64, 128, 256}.
     workspace: any contiguous GPU tensor of at least fa2_decode_paged_multi_plan(...)[2] bytes; allocated here on the current stream when None
     and the plan splits the keys. Deterministic. C entry cln_fa2_decode_paged_multi (include/cln_amd_ext.h); no CPU path."""
-    fn = _ext_fn("cln_fa2_decode_paged_multi", [ctypes.c_void_p] * 8 + [ctypes.c_longlong] + [ctypes.c_int] * 8 + [ctypes.c_void_p])
-    for t in (q, k_pages, v_pages, out):
-        _check_dtype(t, torch.float16)
-    _check_dtype(block_table, torch.int32)
-    _check_dtype(seqlens, torch.int32)
-    _check_dev(q, k_pages, v_pages, block_table, seqlens, out)
-    if q.dim() != 4 or k_pages.dim() != 4 or block_table.dim() != 2:
-        raise RuntimeError("Tensor size mismatch!")
-    B, T, Hq, D = q.shape
-    P, Hkv, page = k_pages.shape[:3]
-    max_pages = block_table.shape[1]
-    _check_shape(k_pages, P, Hkv, page, D)
-    _check_shape(v_pages, P, Hkv, page, D)
-    _check_shape(block_table, B, max_pages)
-    _check_shape(out, B, T, Hq, D)
-    _check_shape(seqlens, B)
-    if lse is not None:
-        _check_dtype(lse, torch.float32)
-        _check_dev(lse)
-        _check_shape(lse, B, T, Hq)
-    need = fa2_decode_paged_multi_plan(B, T, Hq, Hkv, max_pages, page, D)[2]
-    if workspace is None and need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
-    ws_ptr, ws_bytes = None, 0
-    if workspace is not None:
-        _check_dev(workspace)
-        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-        if ws_bytes < need:
-            raise RuntimeError("fa2_decode_paged_multi: workspace of %d bytes, the plan needs %d (fa2_decode_paged_multi_plan)" % (ws_bytes, need))
-    rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), out.data_ptr(),
-            None if lse is None else lse.data_ptr(), ws_ptr, ws_bytes, B, T, Hq, Hkv, P, max_pages, page, D, _stream())
-    _raise("fa2_decode_paged_multi", rc)
+    _paged_decode("fa2_decode_paged_multi", fa2_decode_paged_multi_plan, 4, q, k_pages, v_pages, block_table, seqlens, out, lse, workspace)

@@ -17,6 +17,7 @@ HDR = os.path.join(ROOT, "include", "cln_amd_ext.h")
 CSRC = os.path.join(ROOT, "cuda-learn-notes_amd", "csrc")
 sys.path.insert(0, os.path.join(ROOT, "cuda-learn-notes_amd", "tools"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import decode_kernels as dk  # noqa: E402
 import multi_decode_reference as mr  # noqa: E402
 import paged_decode_reference as pr  # noqa: E402
 from test_fragment_layout_model import ds_read_b64_tr_b16, lds_halves, mfma_16x16x32  # noqa: E402
@@ -151,7 +152,7 @@ def test_plan_grid(built):
             t = m.describe_decode_paged_multi(B, T, Hq, Hkv, mp, page, D)
             tiles = -(-T * G // mr.TILE_ROWS)
             assert t.startswith("fa2_decode_paged_multi<D=%d,MT=%d> T=%d G=%d S=%d C=%d page=%d:" % (D, tiles, T, G, S, C, page)), t
-            assert ("; then fa2_decode_paged_multi_combine<D=%d>" % D in t) == (S > 1), t
+            assert ("; then fa2_decode_combine<D=%d>" % D in t) == (S > 1), t
             assert "v_mfma_f32_16x16x32_f16" in t and t.endswith("deterministic"), t
             if S > 1:
                 assert "workspace %d bytes" % need in t, t
@@ -292,10 +293,21 @@ def test_names_stay_off_the_manifest_surface(built):
     assert not any(n + "(" in gen for n in NAMES)
 
 
+def test_multi_kernels_in_the_product_library_are_exactly_the_plannable_ones(built):
+    from cuda_learn_notes_amd import _loader
+    linked = {k for k in dk.linked(_loader.so_path("libcln_amd.so")) if k[0] in ("fa2_decode_paged_multi", "fa2_decode_combine")}
+    plannable = set()
+    for (B, T, Hq, Hkv, mp, page, D) in grid():
+        if mp == 63:
+            plannable |= dk.named(built.manifest.describe_decode_paged_multi(B, T, Hq, Hkv, mp, page, D))
+    assert len(plannable) == 2 * 4 + 2, sorted(plannable)  # D x row tiles, and the two combines
+    assert linked == plannable, sorted(linked ^ plannable)
+
+
 def test_kernels_run_both_products_on_the_matrix_pipe_and_keep_registers(tmp_path):
     import kernel_resources as kr
     kernels, s = kr.report(os.path.join(CSRC, "flash_attn_decode_paged_multi.hip"), keep=str(tmp_path))
-    ks = [k for k in kernels if "fa2pm::" in k["demangled"]]
+    ks = [k for k in kernels if "fa2pm::" in k["demangled"] or "fa2d::" in k["demangled"]]
     assert len(ks) == 2 * 4 + 2 and len(kernels) == len(ks), [k["demangled"] for k in kernels]  # D x row tiles, and the two combines
     text = open(s).read()
     for k in ks:

@@ -1,6 +1,6 @@
 """CPU: the paged decode attention entries (include/cln_amd_ext.h: cln_fa2_decode_paged_plan, cln_fa2_decode_paged,
 cln_fa2_decode_paged_describe; csrc/flash_attn_decode_paged.hip) -- header, exports, argument checks before any device access, the plan against its
-Python mirror and the describe text, the references of tests/paged_decode_reference.py, "linked == plannable" for the fa2p:: kernels, and their
+Python mirror and the describe text, the references of tests/paged_decode_reference.py, "linked == plannable" for the paged kernels, and their
 code (no spill, no scratch, 16-byte loads). No GPU needed: hipcc cross-compiles."""
 import ctypes
 import os
@@ -17,6 +17,7 @@ HDR = os.path.join(ROOT, "include", "cln_amd_ext.h")
 CSRC = os.path.join(ROOT, "cuda-learn-notes_amd", "csrc")
 sys.path.insert(0, os.path.join(ROOT, "cuda-learn-notes_amd", "tools"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import decode_kernels as dk  # noqa: E402
 import decode_reference as dr  # noqa: E402
 import paged_decode_reference as pr  # noqa: E402
 
@@ -143,7 +144,7 @@ def test_plan_grid(built):
         assert need == (B * Hq * S * (D + 2) * 4 if S > 1 else 0)
         t = m.describe_decode_paged(B, Hq, Hkv, mp, page, D)
         assert t.startswith("fa2_decode_paged<D=%d,G=%d> S=%d C=%d page=%d:" % (D, G, S, C, page)), t
-        assert ("; then fa2_decode_paged_combine<D=%d>" % D in t) == (S > 1), t
+        assert ("; then fa2_decode_combine<D=%d>" % D in t) == (S > 1), t
         assert t.endswith("deterministic"), t
         if S > 1:
             assert "workspace %d bytes" % need in t, t
@@ -243,31 +244,12 @@ def test_names_stay_off_the_manifest_surface(built):
     assert "fa2_decode_paged" not in fast
 
 
-def _fa2p_kernels(so):
-    nm, filt = shutil.which("nm"), shutil.which("c++filt")
-    if not nm or not filt:
-        pytest.skip("binutils nm / c++filt not available")
-    out = subprocess.run([nm, so], capture_output=True, text=True, check=True).stdout
-    names = [ln.split()[2] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "VvWwDd" and "_kernel" in ln and "__device_stub__" not in ln]
-    dem = subprocess.run([filt], input="\n".join(n.replace("DF16_", "Dh") for n in names), capture_output=True, text=True, check=True).stdout
-    res = set()
-    for d in dem.splitlines():
-        mm = re.match(r"(?:void )?((?:\w+::)*\w+_kernel)(?:<(.*?)>)?\(", d)
-        if mm and mm.group(1).startswith("fa2p::"):
-            res.add((mm.group(1).split("::")[1],) + tuple(int(x) for x in mm.group(2).split(",")))
-    return res
-
-
 def test_fa2p_kernels_in_the_product_library_are_exactly_the_plannable_ones(built):
     from cuda_learn_notes_amd import _loader
-    linked = _fa2p_kernels(_loader.so_path("libcln_amd.so"))
+    linked = {k for k in dk.linked(_loader.so_path("libcln_amd.so")) if k[0] in ("fa2_decode_paged", "fa2_decode_combine")}
     plannable = set()
     for (B, Hq, Hkv, mp, page, D) in grid():
-        t = built.manifest.describe_decode_paged(B, Hq, Hkv, mp, page, D)
-        for k in re.findall(r"fa2_decode_paged<D=(\d+),G=(\d+)>", t):
-            plannable.add(("fa2_decode_paged_kernel", int(k[0]), int(k[1])))
-        for k in re.findall(r"fa2_decode_paged_combine<D=(\d+)>", t):
-            plannable.add(("fa2_decode_paged_combine_kernel", int(k)))
+        plannable |= dk.named(built.manifest.describe_decode_paged(B, Hq, Hkv, mp, page, D))
     assert len(plannable) == 2 * len(pr.GROUPS) + 2, sorted(plannable)
     assert linked == plannable, sorted(linked ^ plannable)
 
@@ -275,7 +257,7 @@ def test_fa2p_kernels_in_the_product_library_are_exactly_the_plannable_ones(buil
 def test_fa2p_kernels_keep_registers_and_load_16_bytes(tmp_path):
     import kernel_resources as kr
     kernels, s = kr.report(os.path.join(CSRC, "flash_attn_decode_paged.hip"), keep=str(tmp_path))
-    ks = [k for k in kernels if "fa2p::" in k["demangled"]]
+    ks = [k for k in kernels if "fa2d::" in k["demangled"]]
     assert len(ks) == 2 * len(pr.GROUPS) + 2 and len(kernels) == len(ks), [k["demangled"] for k in kernels]
     text = open(s).read()
     for k in ks:
@@ -283,8 +265,8 @@ def test_fa2p_kernels_keep_registers_and_load_16_bytes(tmp_path):
         body = text[text.index("\n" + k["name"] + ":"):]
         body = body[:body.index(".Lfunc_end")]
         assert "v_mfma" not in body and "atomic" not in body, k["demangled"]
-        if "fa2_decode_paged_kernel" in k["demangled"]:
+        if "fa2_decode_kernel" in k["demangled"]:
             assert "global_load_dwordx4" in body, k
-            if re.search(r"<\d+, 1>", k["demangled"]):
+            if re.search(r"<\d+, 1, ", k["demangled"]):
                 assert k["vgpr"] <= 128, k  # G = 1: at least four waves per SIMD, like fa2d::
             assert k["vgpr"] + k["agpr"] <= 512, k

@@ -4,7 +4,6 @@ tests/decode_reference.py, "linked == plannable" for the fa2d:: kernels, and the
 cross-compiles."""
 import ctypes
 import os
-import re
 import shutil
 import subprocess
 import sys
@@ -17,6 +16,7 @@ HDR = os.path.join(ROOT, "include", "cln_amd_ext.h")
 CSRC = os.path.join(ROOT, "cuda-learn-notes_amd", "csrc")
 sys.path.insert(0, os.path.join(ROOT, "cuda-learn-notes_amd", "tools"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import decode_kernels as dk  # noqa: E402
 import decode_reference as dr  # noqa: E402
 
 NAMES = ("cln_fa2_decode_plan", "cln_fa2_decode")
@@ -208,34 +208,17 @@ def test_names_stay_off_the_manifest_surface(built):
     assert "fa2_decode" not in fast
 
 
-def _fa2d_kernels(so):
-    nm, filt = shutil.which("nm"), shutil.which("c++filt")
-    if not nm or not filt:
-        pytest.skip("binutils nm / c++filt not available")
-    out = subprocess.run([nm, so], capture_output=True, text=True, check=True).stdout
-    names = [ln.split()[2] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "VvWwDd" and "_kernel" in ln and "__device_stub__" not in ln]
-    dem = subprocess.run([filt], input="\n".join(n.replace("DF16_", "Dh") for n in names), capture_output=True, text=True, check=True).stdout
-    res = set()
-    for d in dem.splitlines():
-        mm = re.match(r"(?:void )?((?:\w+::)*\w+_kernel)(?:<(.*?)>)?\(", d)
-        if mm and mm.group(1).startswith("fa2d::"):
-            res.add((mm.group(1).split("::")[1], int(mm.group(2))))
-    return res
-
-
 def test_fa2d_kernels_in_the_product_library_are_exactly_the_plannable_ones(built):
     from cuda_learn_notes_amd import _loader
-    linked = _fa2d_kernels(_loader.so_path("libcln_amd.so"))
+    linked = {k for k in dk.linked(_loader.so_path("libcln_amd.so")) if k[0] in ("fa2_decode", "fa2_decode_combine")}
     plannable = set()
     for D in (32, 64, 96, 128, 256):
         for (B, H) in BHS:
             for Nmax in NMAXS:
                 try:
-                    t = built.manifest.describe("cln_fa2_decode", (B, H, Nmax, D), 2)
+                    plannable |= dk.named(built.manifest.describe("cln_fa2_decode", (B, H, Nmax, D), 2))
                 except ValueError:
                     continue
-                for k in re.findall(r"(fa2_decode|fa2_decode_combine)<D=(\d+)>", t):
-                    plannable.add((k[0] + "_kernel", int(k[1])))
     assert len(plannable) == 4, sorted(plannable)
     assert linked == plannable, sorted(linked ^ plannable)
 
