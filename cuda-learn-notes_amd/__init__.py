@@ -89,6 +89,21 @@ def fa2_decode_paged_multi_plan(B, T, Hq, Hkv, max_pages, page, D):
     return host.fa2_decode_paged_multi_plan(B, T, Hq, Hkv, max_pages, page, D)
 
 
+def kv_append_paged(k_new, v_new, k_pages, v_pages, block_table, seqlens, q=None, q_out=None, rope_table=None, rope="none"):
+    """Write the K / V rows of T new tokens per sequence into a paged KV cache (the pools, table and lengths of fa2_decode_paged_multi; the
+    lengths count the new tokens), with the rotary embedding of K and q fused in: k_new, v_new fp16 [B,T,Hkv,D], q / q_out fp16 [B,T,Hq,D] or
+    None (q_out may be q), rope_table fp32 [max_pos,D] (kv_append_rope_table), rope "none", "half" (pairs (i, i + D/2)) or "interleaved"
+    (pairs (2i, 2i+1)). One launch, nothing read on the host. C entry cln_kv_append_paged (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.kv_append_paged(k_new, v_new, k_pages, v_pages, block_table, seqlens, q, q_out, rope_table, rope)
+
+
+def kv_append_rope_table(max_pos, D, theta=10000.0, device=None):
+    """fp32 [max_pos, D] for kv_append_paged: row p = cos(p f_i) for i < D/2, then sin(p f_i), f_i = theta^(-2i/D), angles formed in float64."""
+    from . import host
+    return host.kv_append_rope_table(max_pos, D, theta, device)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

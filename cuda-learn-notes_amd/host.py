@@ -829,3 +829,75 @@ def fa2_decode_paged_multi(q, k_pages, v_pages, block_table, seqlens, out, lse=N
     workspace: any contiguous GPU tensor of at least fa2_decode_paged_multi_plan(...)[2] bytes; allocated here on the current stream when None
     and the plan splits the keys. Deterministic. C entry cln_fa2_decode_paged_multi (include/cln_amd_ext.h); no CPU path."""
     _paged_decode("fa2_decode_paged_multi", fa2_decode_paged_multi_plan, 4, q, k_pages, v_pages, block_table, seqlens, out, lse, workspace)
+
+
+_ROPE_MODES = {"none": 0, "half": 1, "interleaved": 2}
+
+
+def kv_append_rope_table(max_pos, D, theta=10000.0, device=None):
+    """The cos / sin table kv_append_paged rotates with: fp32 [max_pos, D], row p = cos(p f_i) for i < D/2, then sin(p f_i), with
+    f_i = theta^(-2i/D). The angles are formed in float64 and cast once."""
+    max_pos, D = int(max_pos), int(D)
+    if max_pos <= 0 or D <= 0 or D % 2:
+        raise RuntimeError("kv_append_rope_table: max_pos %d and an even D %d must be positive" % (max_pos, D))
+    freq = torch.tensor(float(theta), dtype=torch.float64) ** (-2.0 * torch.arange(D // 2, dtype=torch.float64) / D)
+    ang = torch.arange(max_pos, dtype=torch.float64)[:, None] * freq[None, :]
+    return torch.cat((torch.cos(ang), torch.sin(ang)), dim=1).to(torch.float32).to(device)
+
+
+def kv_append_paged(k_new, v_new, k_pages, v_pages, block_table, seqlens, q=None, q_out=None, rope_table=None, rope="none"):
+    """Write the K / V rows of T new tokens per sequence into a paged KV cache, with the rotary embedding of K and q fused in; one launch.
+    k_new, v_new fp16 [B,T,Hkv,D]; k_pages, v_pages fp16 [P,Hkv,page,D], written in place; block_table int32 [B,max_pages] and seqlens int32 [B]
+    on the GPU (never read by the host). seqlens[b] counts the T new tokens, as for fa2_decode_paged_multi: token t stands at
+    pos = seqlens[b] - T + t and is live iff 0 <= pos < max_pages * page (and pos < max_pos with a rotation); a live token's rows go to row
+    pos % page of page block_table[b, pos // page], a token that is not live writes nothing to the pools and zeros to its q_out rows.
+    rope: "none" (rows copied bit for bit; q, q_out, rope_table must be None), "half" (pairs (i, i + D/2)) or "interleaved" (pairs (2i, 2i+1)),
+    rotated in fp32 by rope_table fp32 [max_pos, D] (kv_append_rope_table) with one rounding; V is never rotated. q, q_out fp16 [B,T,Hq,D],
+    given together or both None; q_out may be q. The live table entries must lie in [0, P) and name distinct pages. D in {64, 128}, page in
+    {16, 32, 64, 128, 256}, Hq a multiple of Hkv, any T. Deterministic. C entry cln_kv_append_paged (include/cln_amd_ext.h); no CPU path."""
+    fn = _ext_fn("cln_kv_append_paged", [ctypes.c_void_p] * 9 + [ctypes.c_int] * 10 + [ctypes.c_void_p])
+    if rope not in _ROPE_MODES:
+        raise RuntimeError("kv_append_paged: rope %r not supported ('none', 'half' or 'interleaved')" % (rope,))
+    mode = _ROPE_MODES[rope]
+    if mode == 0 and not (q is None and q_out is None and rope_table is None):
+        raise RuntimeError("kv_append_paged: rope 'none' takes no q, q_out or rope_table")
+    if mode != 0 and rope_table is None:
+        raise RuntimeError("kv_append_paged: rope %r needs a rope_table (kv_append_rope_table)" % (rope,))
+    if (q is None) != (q_out is None):
+        raise RuntimeError("kv_append_paged: q and q_out are given together or not at all")
+    halves = (k_new, v_new, k_pages, v_pages) + ((q, q_out) if q is not None else ())
+    _decode_check(halves, (block_table, seqlens))
+    if k_new.dim() != 4 or k_pages.dim() != 4 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    B, T, Hkv, D = k_new.shape
+    P, _, page, _ = k_pages.shape
+    max_pages = block_table.shape[1]
+    _check_shape(v_new, B, T, Hkv, D)
+    _check_shape(k_pages, P, Hkv, page, D)
+    _check_shape(v_pages, P, Hkv, page, D)
+    _check_shape(block_table, B, max_pages)
+    _check_shape(seqlens, B)
+    Hq, max_pos = Hkv, 0
+    if q is not None:
+        if q.dim() != 4:
+            raise RuntimeError("Tensor size mismatch!")
+        Hq = q.shape[2]
+        _check_shape(q, B, T, Hq, D)
+        _check_shape(q_out, B, T, Hq, D)
+    if rope_table is not None:
+        _check_dtype(rope_table, torch.float32)
+        _check_dev(rope_table)
+        if rope_table.dim() != 2:
+            raise RuntimeError("Tensor size mismatch!")
+        max_pos = rope_table.shape[0]
+        _check_shape(rope_table, max_pos, D)
+    if D not in (64, 128):
+        raise RuntimeError("kv_append_paged: headdim %d not supported (64 or 128)" % D)
+    if page not in _PAGED_PAGES:
+        raise RuntimeError("kv_append_paged: page size %d not supported (16, 32, 64, 128 or 256)" % page)
+    if Hq % Hkv:
+        raise RuntimeError("kv_append_paged: %d query heads are no multiple of %d KV heads" % (Hq, Hkv))
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    rc = fn(k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), ptr(q),
+            ptr(q_out), ptr(rope_table), B, T, Hq, Hkv, P, max_pages, page, D, max_pos, mode, _stream())
+    _raise("kv_append_paged", rc, "kv_append_paged: max_pages * page or B * T too large for one launch")

@@ -435,3 +435,21 @@ def stages_honoured(name, dims, stages=2):
     if rc < 0:
         raise ValueError("%s: shape %s not supported (status %d)" % (name, tuple(dims), rc))
     return bool(rc)
+
+
+def describe_kv_append_paged(B, T, Hq, Hkv, max_pages, page, D, rope_mode):
+    """describe() for cln_kv_append_paged (include/cln_amd_ext.h): the kernel instantiation and the launch as text, from
+    cln_kv_append_paged_describe (no GPU needed). rope_mode: 0 / "none", 1 / "half", 2 / "interleaved". ValueError for an unsupported or invalid
+    shape."""
+    import ctypes
+    from . import _loader
+    mode = {"none": 0, "half": 1, "interleaved": 2}.get(rope_mode, rope_mode)
+    if not isinstance(mode, int):
+        raise ValueError("cln_kv_append_paged: rope %r not supported" % (rope_mode,))
+    fn = _loader.load_so("libcln_amd.so").cln_kv_append_paged_describe
+    fn.argtypes, fn.restype = [ctypes.c_int] * 8 + [ctypes.c_char_p, ctypes.c_int], ctypes.c_int
+    buf = ctypes.create_string_buffer(768)
+    rc = fn(int(B), int(T), int(Hq), int(Hkv), int(max_pages), int(page), int(D), mode, buf, 768)
+    if rc < 0:
+        raise ValueError("cln_kv_append_paged: shape %s not supported (status %d)" % ((B, T, Hq, Hkv, max_pages, page, D, rope_mode), rc))
+    return buf.value.decode()

@@ -108,6 +108,37 @@ int cln_fa2_decode_paged_multi(const void* q, const void* k_pages, const void* v
                                int D, void* stream);
 int cln_fa2_decode_paged_multi_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len);
 
+/* ---- Append to the same PAGED KV cache, with the rotary embedding fused in: the part of a decode step in front of the attention call, as one
+ * launch with no workspace. seqlens[b] counts the T new tokens, exactly as for cln_fa2_decode_paged_multi, so the same tensor feeds the attention
+ * call that follows on the same stream. Token t of sequence b stands at pos = seqlens[b] - T + t (formed in 64 bits: any int32 value is safe) and is
+ * LIVE iff 0 <= pos < max_pages page and, with a rotation, pos < max_pos. For every KV head h a live token's rows go to
+ *   k_pages[block_table[b, pos / page], h, pos % page, :] = rot(k_new[b,t,h,:]),   v_pages[same place] = v_new[b,t,h,:] (never rotated),
+ * and q_out[b,t,h,:] = rot(q[b,t,h,:]). A token that is not live writes nothing to the pools, and its q_out rows are written as zeros.
+ * k_new, v_new: fp16 [B,T,Hkv,D]; k_pages, v_pages: fp16 [P,Hkv,page,D], written in place; block_table: int32 [B,max_pages] and seqlens: int32 [B],
+ * both ON THE DEVICE and never read by the host; q: fp16 [B,T,Hq,D] or NULL; q_out: fp16 [B,T,Hq,D] or NULL;
+ * rope_table: fp32 [max_pos,D] or NULL, row p = cos(p f_0) .. cos(p f_{D/2-1}), then sin(p f_0) .. sin(p f_{D/2-1}).
+ * rope_mode 0: none -- K and V are copied bit for bit; q, q_out and rope_table must all be NULL. 1: half-split pairs (i, i + D/2) (NeoX / Llama).
+ * 2: interleaved pairs (2i, 2i + 1). For 1 and 2, pair i of a live token becomes (x1 c - x2 s, x1 s + x2 c) with c = rope_table[pos, i] and
+ * s = rope_table[pos, D/2 + i]: products and sums in fp32, one rounding to fp16 at the store; full width only. It is applied to K and, when q and
+ * q_out are given (together, or both NULL), to q. q_out == q is allowed; every other equality among k_pages, v_pages, q_out or between one of them
+ * and an input is rejected.
+ * Read: seqlens[b], the entry block_table[b, pos / page] and row pos of rope_table of live tokens, and the new rows. Written: the live rows only;
+ * every other byte of both pools is untouched. THE CALLER'S CONTRACT, not checked: the live entries lie in [0, P), and no two live (sequence, page
+ * index) pairs name the same physical page.
+ * Supported: D in {64, 128}; page in {16, 32, 64, 128, 256}; any Hq that is a multiple of Hkv; any T >= 1 (a prompt chunk is appended with the same
+ * call); any B, P, max_pages >= 1 with max_pages page < 2^31. Deterministic, no atomics, no library state.
+ * Returns 0, -1 (null k_new / v_new / k_pages / v_pages / block_table / seqlens; the pointer rules of rope_mode; a tensor pointer that is not 16-byte
+ * aligned or a block_table / seqlens / rope_table pointer that is not 4-byte aligned; a non-positive dimension, or max_pos <= 0 with a rotation;
+ * Hq % Hkv != 0; forbidden aliasing), -2 (other D, page or rope_mode; max_pages page >= 2^31; a grid that does not fit) -- all checked before any
+ * device access -- or -3 (launch error).
+ * cln_kv_append_paged_describe writes the kernel instantiation and the launch as text into buf (at most len bytes, NUL-terminated; with a rotation
+ * it counts the q rows) and returns the text's length, or the same -1 / -2.
+ */
+int cln_kv_append_paged(const void* k_new, const void* v_new, void* k_pages, void* v_pages, const int* block_table, const int* seqlens,
+                        const void* q, void* q_out, const float* rope_table, int B, int T, int Hq, int Hkv, int P, int max_pages, int page, int D,
+                        int max_pos, int rope_mode, void* stream);
+int cln_kv_append_paged_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int rope_mode, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
