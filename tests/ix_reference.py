@@ -143,17 +143,19 @@ def abs_sum_bound(a, b):
 
 
 def half_rne(v):
-    """int64 -> the nearest half, ties to even, in integer arithmetic (|v| < 65520); returned as float16."""
+    """int64 -> the nearest half, ties to even, in integer arithmetic; |v| >= 65520 (the tie between 65504, the largest finite half, and 2^16,
+    which goes to the even side, away from 65504) gives +-inf; returned as float16."""
     v = v.to(torch.int64)
     mag = v.abs()
-    assert int(mag.max()) < 65520
     out = mag.clone()
     for sh in range(1, 6):  # mag in [2^(10 + sh), 2^(11 + sh)): the half grid there has spacing 2^sh
         sel = (mag >= (1 << (10 + sh))) & (mag < (1 << (11 + sh)))
         q, r, halfway = mag >> sh, mag & ((1 << sh) - 1), 1 << (sh - 1)
         up = (r > halfway) | ((r == halfway) & ((q & 1) == 1))
         out = torch.where(sel, (q + up.long()) << sh, out)
-    return (torch.sign(v) * out).double().to(torch.float16)
+    res = (torch.sign(v) * out).double()
+    res = torch.where(mag >= 65520, torch.sign(v).double() * float("inf"), res)
+    return res.to(torch.float16)
 
 
 def hgemv_bound(ref, K):
