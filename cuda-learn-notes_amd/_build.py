@@ -26,7 +26,7 @@ LIBDIR = os.path.join(PKG_DIR, "lib")
 ARCH = "gfx950"
 KERNEL_SOURCES = [
     "elementwise.hip", "activation.hip", "blas1.hip", "indexing.hip", "reduce.hip", "softmax.hip", "norm.hip", "rope.hip",
-    "sgemm.hip", "stream_scratch.hip", "hgemm.hip", "hgemm_ring_nn.hip", "hgemm_ring_tn.hip", "flash_attn.hip", "flash_attn_m16x.hip", "flash_attn_causal.hip", "flash_attn_fwd_lse.hip", "flash_attn_bwd.hip", "flash_attn_decode.hip", "flash_attn_decode_paged.hip", "flash_attn_decode_paged_multi.hip", "kv_append_paged.hip", "describe.hip",
+    "sgemm.hip", "stream_scratch.hip", "hgemm.hip", "hgemm_ring_nn.hip", "hgemm_ring_tn.hip", "flash_attn.hip", "flash_attn_m16x.hip", "flash_attn_m16x_ext.hip", "flash_attn_bwd.hip", "flash_attn_decode.hip", "flash_attn_decode_paged.hip", "flash_attn_decode_paged_multi.hip", "kv_append_paged.hip", "describe.hip",
 ]
 VENDOR_SOURCES = ["hgemm_vendor.hip", "hgemm_vendor_lt.hip", "fa2_vendor_ck.hip", "yardstick_vendor.hip"]  # the last: ck_tile FMHA instances (~1 min of hipcc)
 # a comparison row whose sources are the ROCm image's ck_tile headers: if they are missing or do not compile, the vendor
@@ -39,7 +39,7 @@ PROBE_SHARED = ["hgemm_ring_nn.hip", "hgemm_ring_tn.hip"]
 CFLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-ffp-contract=fast",
           "-I" + CSRC, "-I" + os.path.join(CSRC, "probe")]
 # per-file additions (the reason is stated at the top of each file)
-EXTRA_FLAGS = {"flash_attn_m16x.hip": ["-fno-slp-vectorize"], "flash_attn_causal.hip": ["-fno-slp-vectorize"], "flash_attn_fwd_lse.hip": ["-fno-slp-vectorize"],
+EXTRA_FLAGS = {"flash_attn_m16x.hip": ["-fno-slp-vectorize"], "flash_attn_m16x_ext.hip": ["-fno-slp-vectorize"],
                "flash_attn_bwd.hip": ["-fno-slp-vectorize"], "probe/flash_attn_m16x_probe.hip": ["-fno-slp-vectorize"],
                "fa2_vendor_ck.hip": ["-I/opt/rocm/include", "-Wno-everything"]}
 

@@ -15,8 +15,7 @@
 int cln_hgemm_describe(const char* name, int M, int N, int K, int stages, char* buf, int len);
 int cln_fa_describe(const char* name, int B, int H, int N, int D, int stages, char* buf, int len);
 int cln_sgemm_describe(const char* name, int M, int N, int K, int stages, char* buf, int len);
-int cln_fa_causal_describe(const char* name, int B, int H, int N, int D, int stages, char* buf, int len);  // flash_attn_causal.hip (cln_amd_ext.h)
-int cln_fa_lse_describe(const char* name, int B, int H, int N, int D, int stages, char* buf, int len);     // flash_attn_fwd_lse.hip (cln_amd_ext.h)
+int cln_fa_m16x_ext_describe(const char* name, int B, int H, int N, int D, int stages, char* buf, int len);  // flash_attn_m16x_ext.hip (cln_amd_ext.h)
 int cln_fa_bwd_describe(const char* name, int B, int H, int N, int D, int stages, char* buf, int len);     // flash_attn_bwd.hip (cln_amd_ext.h)
 int cln_fa_decode_describe(const char* name, int B, int H, int Nmax, int D, int stages, char* buf, int len);  // flash_attn_decode.hip (cln_amd_ext.h)
 
@@ -24,9 +23,7 @@ CLN_API int cln_describe(const char* name, int d0, int d1, int d2, int d3, int s
   if (!name || !buf || buflen <= 0) return CLN_ERR_BAD_ARG;
   int rc = cln_fa_describe(name, d0, d1, d2, d3, stages, buf, buflen);
   if (rc != CLN_ERR_BAD_ARG) return rc;
-  rc = cln_fa_causal_describe(name, d0, d1, d2, d3, stages, buf, buflen);
-  if (rc != CLN_ERR_BAD_ARG) return rc;
-  rc = cln_fa_lse_describe(name, d0, d1, d2, d3, stages, buf, buflen);
+  rc = cln_fa_m16x_ext_describe(name, d0, d1, d2, d3, stages, buf, buflen);
   if (rc != CLN_ERR_BAD_ARG) return rc;
   rc = cln_fa_bwd_describe(name, d0, d1, d2, d3, stages, buf, buflen);
   if (rc != CLN_ERR_BAD_ARG) return rc;

@@ -1,5 +1,5 @@
 // FlashAttention-2 backward, head dims 64 / 128, causal (key <= query) or not: dQ, dK, dV from Q, K, V, O, dO and the forward's
-// row log-sum-exp (flash_attn_fwd_lse.hip). Two kernels on the stream, each output element summed by ONE wave in a fixed order
+// row log-sum-exp (flash_attn_m16x_ext.hip). Two kernels on the stream, each output element summed by ONE wave in a fixed order
 // (bit-repeatable; no float atomics):
 //   fa2_bwd_dq_kernel    owned by a 128-row query block: writes delta = rowsum(dO o O) for its rows, then walks its key tiles
 //                        (causal: up to the diagonal) -- S^T = K Q'^T, dP^T = V dO^T, dS^T = P^T o (dP^T - delta), dQ^T += K^T dS^T;

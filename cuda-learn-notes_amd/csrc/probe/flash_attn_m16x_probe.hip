@@ -5,19 +5,20 @@
 // steps into v_pk_add_f32, which drags the exponentials of a whole phase behind its last MFMA and is slower than two
 // plain adds beside MFMAs (MI355X_MICROARCH.md, per-instruction constants). Linked into the probe library only.
 #include "flash_attn_m16x.cuh"
-#include "flash_attn_causal.cuh"
 #include "flash_attn_m16s.cuh"
 #include "flash_attn_m32x.cuh"
 #include "flash_attn_m16x_api.h"
 
 namespace fa2 {
 
-// the causal kernel (flash_attn_causal.cuh, stages = 2) in each launch order M16X_ORDER_* (the product ships one of them: flash_attn_causal.hip)
+unsigned long long* g_m16x_stamps = nullptr;  // device buffer of the M16X_STAMP forms (10 words per wave), cln_probe_set_stamps
+
+// the causal kernel (stages = 2) in each launch order M16X_ORDER_* (the product ships one of them: flash_attn_m16x_ext.hip)
 int m16x_causal_probe_run(int D, int order, const void* q, const void* k, const void* v, void* o, int B, int H, int N, hipStream_t s) {
   if (N % 256 != 0) return CLN_ERR_UNSUPPORTED;
-  if (order == M16X_ORDER_PLAIN) return fa2c::run_causal<M16X_ORDER_PLAIN>(D, false, q, k, v, o, B, H, N, s);
-  if (order == M16X_ORDER_HEAVY) return fa2c::run_causal<M16X_ORDER_HEAVY>(D, false, q, k, v, o, B, H, N, s);
-  if (order == M16X_ORDER_HEAD_REV) return fa2c::run_causal<M16X_ORDER_HEAD_REV>(D, false, q, k, v, o, B, H, N, s);
+  if (order == M16X_ORDER_PLAIN) return launch_m16x_shipped<M16X_SHIPPED, false, true, M16X_ORDER_PLAIN>(D, 32, q, k, v, o, nullptr, B, H, N, s);
+  if (order == M16X_ORDER_HEAVY) return launch_m16x_shipped<M16X_SHIPPED, false, true, M16X_ORDER_HEAVY>(D, 32, q, k, v, o, nullptr, B, H, N, s);
+  if (order == M16X_ORDER_HEAD_REV) return launch_m16x_shipped<M16X_SHIPPED, false, true, M16X_ORDER_HEAD_REV>(D, 32, q, k, v, o, nullptr, B, H, N, s);
   return CLN_ERR_UNSUPPORTED;
 }
 
@@ -25,7 +26,7 @@ int m16x_causal_probe_run(int D, int order, const void* q, const void* k, const 
 // 120 + 16 * (NDEF - 1) + OX: 64 rows per wave (D = 64, 64-key tiles)
 int m16x_probe_run(int D, int code, const void* q, const void* k, const void* v, void* o, int B, int H, int N, hipStream_t s) {
 #define MX(DD, CODE, RPWW, BCC, PDD, NDEFF, OXX) \
-  if (D == DD && code == CODE) return launch_m16x<DD, RPWW, BCC, PDD, NDEFF, OXX>(q, k, v, o, B, H, N, s);
+  if (D == DD && code == CODE) return launch_m16x<DD, RPWW, BCC, PDD, NDEFF, OXX>(q, k, v, o, ((OXX) & M16X_STAMP) != 0 ? g_m16x_stamps : nullptr, B, H, N, s);
   MX(64, 5, 32, 128, 8, 1, 5) MX(64, 21, 32, 128, 8, 2, 5) MX(64, 33, 32, 128, 8, 3, 1) MX(64, 37, 32, 128, 8, 3, 5) MX(64, 38, 32, 128, 8, 3, 6)
   MX(64, 48, 32, 128, 8, 4, 0) MX(64, 49, 32, 128, 8, 4, 1) MX(64, 53, 32, 128, 8, 4, 5) MX(64, 54, 32, 128, 8, 4, 6) MX(64, 52, 32, 128, 8, 4, 4)
   MX(64, 69, 32, 128, 8, 5, 5) MX(64, 85, 32, 128, 8, 6, 5)

@@ -164,7 +164,7 @@ CLN_API int cln_fa2_variant(int D, int nw, int vt, int opt, int abl, const void*
   if (D == 512 && abl == 546) return fa2::launch_m16_pair<2, true, false, 131072>(q, k, v, o, B, H, N, (hipStream_t)stream);
   // 800.. = the sum-checked optimistic softmax form (flash_attn_m16x.cuh, its own compile unit): abl = 800 + code,
   //         code = 16 * (NDEF - 1) + OX (OX: 1 = phase-A priority, 4 = split prologue); 860.. = prefetch depth 4; 880.. = 64 rows per wave
-  // 2700 + order = the causal kernel (flash_attn_causal.cuh, stages = 2) in launch order M16X_ORDER_* (0 plain, 1 heaviest first, 2 heads reversed)
+  // 2700 + order = the causal kernel (flash_attn_m16x.cuh CAUSAL, stages = 2) in launch order M16X_ORDER_* (0 plain, 1 heaviest first, 2 heads reversed)
   if (abl >= 2700 && abl < 2703) return fa2::m16x_causal_probe_run(D, abl - 2700, q, k, v, o, B, H, N, (hipStream_t)stream);
   if (abl >= 800 && abl < 1000 && D <= 128) return fa2::m16x_probe_run(D, abl - 800, q, k, v, o, B, H, N, (hipStream_t)stream);
   // 1300 + opt = the one-wave-per-SIMD kernel for head dims 640 / 768 / 1024 (flash_attn_dw4.cuh, round 5); opt bits: 1 = `stages = 1` form, 2 = running

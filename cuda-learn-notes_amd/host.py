@@ -580,18 +580,10 @@ def fa2_variant(D_nw_vt_opt_abl, Q, K, V, O):
     _raise("cln_fa2_variant", rc, "variant not instantiated / shape not supported")
 
 
-_causal_fn = None
-
-
 def fa2_fwd_causal(Q, K, V, O, stages=2):
     """Causal FlashAttention-2 forward (mask key <= query, scale 1/sqrt(D)) into O: fp16 [B,H,N,D] tensors, D in {64, 128},
     N a multiple of 256. C entry cln_fa2_fwd_causal (include/cln_amd_ext.h); no CPU path."""
-    global _causal_fn
-    if _causal_fn is None:
-        fn = _loader.load_so("libcln_amd.so").cln_fa2_fwd_causal
-        fn.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 + [ctypes.c_void_p]
-        fn.restype = ctypes.c_int
-        _causal_fn = fn
+    fn = _ext_fn("cln_fa2_fwd_causal", [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 + [ctypes.c_void_p])
     for t in (Q, K, V, O):
         _check_dtype(t, torch.float16)
     _check_dev(Q, K, V, O)
@@ -600,12 +592,8 @@ def fa2_fwd_causal(Q, K, V, O, stages=2):
     B, H, N, D = Q.shape
     for t in (K, V, O):
         _check_shape(t, B, H, N, D)
-    rc = _causal_fn(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), B, H, N, D, int(stages), _stream())
-    if rc == -2:
-        if D not in (64, 128):
-            raise RuntimeError("fa2_fwd_causal: headdim %d not supported (64 or 128)" % D)
-        raise RuntimeError("fa2_fwd_causal: seqlen %d must be a multiple of 256" % N)
-    _raise("fa2_fwd_causal", rc)
+    rc = fn(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), B, H, N, D, int(stages), _stream())
+    _check_bh("fa2_fwd_causal", B, H, N, D, rc)
 
 
 _lse_fns = {}

@@ -1,6 +1,6 @@
 """CPU: the attention entries with log-sum-exp and the backward (include/cln_amd_ext.h: cln_fa2_fwd_lse, cln_fa2_fwd_causal_lse, cln_fa2_bwd,
-cln_fa2_bwd_causal; csrc/flash_attn_fwd_lse.hip, csrc/flash_attn_bwd.hip) -- header, exports, argument checks before any device access,
-cln_describe texts, "linked == plannable" for the fa2b:: kernels, and their code (16x16x32 f16 MFMAs only, no spill, no scratch, no MFMA
+cln_fa2_bwd_causal; csrc/flash_attn_m16x_ext.hip, csrc/flash_attn_bwd.hip) -- header, exports, argument checks before any device access,
+cln_describe texts, "linked == plannable" for the LSE forwards (fa2_fwd_m16x_kernel with LSE) and the fa2b:: backward kernels, and their code (16x16x32 f16 MFMAs only, no spill, no scratch, no MFMA
 writing over its own operands). No GPU needed: hipcc cross-compiles."""
 import ctypes
 import os
@@ -18,6 +18,8 @@ SINGLE = " [single stage: every tile fetch waited for where it is issued]"
 FWD = ("cln_fa2_fwd_lse", "cln_fa2_fwd_causal_lse")
 BWD = ("cln_fa2_bwd", "cln_fa2_bwd_causal")
 sys.path.insert(0, os.path.join(ROOT, "cuda-learn-notes_amd", "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_handles import M16X, M16X_CLAIMS, kernel_handles, m16x_args  # noqa: E402
 
 
 @pytest.mark.parametrize("lang,cc", [("c", "gcc"), ("c++", "g++")])
@@ -133,34 +135,21 @@ def test_new_names_stay_off_the_reference_surface(built):
     assert not any(n + "(" in gen for n in FWD + BWD)
 
 
-def _fa2b_kernel_handles(so):
-    nm, filt = shutil.which("nm"), shutil.which("c++filt")
-    if not nm or not filt:
-        pytest.skip("binutils nm / c++filt not available")
-    out = subprocess.run([nm, so], capture_output=True, text=True, check=True).stdout
-    names = [ln.split()[2] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "VvWwDd" and "_kernel" in ln and "__device_stub__" not in ln]
-    dem = subprocess.run([filt], input="\n".join(n.replace("DF16_", "Dh") for n in names), capture_output=True, text=True, check=True).stdout
-    res = []
-    for d in dem.splitlines():
-        mm = re.match(r"(?:void )?((?:\w+::)*\w+_kernel)(?:<(.*?)>)?\(", d)
-        if mm and mm.group(1).startswith("fa2b::"):
-            res.append((mm.group(1), [a.strip() for a in (mm.group(2) or "").split(",")]))
-    return res
-
-
 def test_fa2b_kernels_in_the_product_library_are_exactly_the_plannable_ones(built):
     from cuda_learn_notes_amd import _loader
     linked = set()
-    for fam, a in _fa2b_kernel_handles(_loader.so_path("libcln_amd.so")):
-        causal = a[-1] == "true" if fam != "fa2b::fa2_fwd_m16x_lse_kernel" else a[4] == "true"
-        if fam == "fa2b::fa2_fwd_m16x_lse_kernel":
-            # <D, fragment prefetch depth, deferred key blocks, option bits (5; + 32768 + 2 << 16: single stage), causal, launch order (1: heaviest first)>
-            assert a[1:3] == (["8", "4"] if a[0] == "64" else ["4", "4"]) and a[3] in ("5", "163845"), a
-            assert a[5] == ("1" if causal else "0"), a
-            linked.add(("fwd", int(a[0]), causal, a[3] == "163845"))
-        else:
+    for fam, a in kernel_handles(_loader.so_path("libcln_amd.so")):
+        if fam == M16X and M16X_CLAIMS["lse"](a):
+            # <D, rows per wave, key tile, fragment prefetch depth, deferred key blocks, option bits (5; + 32768 + 2 << 16: single stage), V as [B,H,N,D],
+            # causal, launch order (1: heaviest first), LSE>
+            causal = a[7] == "true"
+            assert a[1:3] == ["32", "128"] and a[6] == "false", a
+            assert a[3:5] == (["8", "4"] if a[0] == "64" else ["4", "4"]) and a[5] in ("5", "163845"), a
+            assert a[8] == ("1" if causal else "0"), a
+            linked.add(("fwd", int(a[0]), causal, a[5] == "163845"))
+        elif fam.startswith("fa2b::"):
             assert fam in ("fa2b::fa2_bwd_dq_kernel", "fa2b::fa2_bwd_dkdv_kernel"), fam
-            linked.add((fam.split("::")[1], int(a[0]), causal, None))
+            linked.add((fam.split("::")[1], int(a[0]), a[-1] == "true", None))
     plannable = set()
     for D in (32, 64, 96, 128, 256):
         for (B, H) in ((1, 1), (1, 8), (2, 96)):
@@ -181,12 +170,13 @@ def test_fa2b_kernels_in_the_product_library_are_exactly_the_plannable_ones(buil
     assert linked == plannable, sorted(linked ^ plannable)
 
 
-@pytest.mark.parametrize("unit,count", [("flash_attn_fwd_lse.hip", 8), ("flash_attn_bwd.hip", 8)])
+@pytest.mark.parametrize("unit,count", [("flash_attn_m16x_ext.hip", 8), ("flash_attn_bwd.hip", 8)])
 def test_fa2b_kernels_use_f16_mfma_only_and_keep_registers(tmp_path, unit, count):
     import kernel_resources as kr
     import mfma_overlap_scan as scan
     kernels, s = kr.report(os.path.join(CSRC, unit), keep=str(tmp_path))
-    ks = [k for k in kernels if "fa2b::" in k["demangled"]]
+    # the backward kernels (fa2b::) and the forwards that feed them (fa2_fwd_m16x_kernel with LSE; the unit's causal forwards: test_fa2_causal_surface.py)
+    ks = [k for k in kernels if "fa2b::" in k["demangled"] or (m16x_args(k["demangled"]) and M16X_CLAIMS["lse"](m16x_args(k["demangled"])))]
     assert len(ks) == count, [k["demangled"] for k in kernels]
     text = open(s).read()
     for k in ks:

@@ -1,5 +1,5 @@
-"""CPU: the causal attention entry cln_fa2_fwd_causal (include/cln_amd_ext.h, csrc/flash_attn_causal.hip) -- header, export, argument
-checks before any device access, cln_describe text, "linked == plannable" for its fa2c:: kernels, and the code of those kernels
+"""CPU: the causal attention entry cln_fa2_fwd_causal (include/cln_amd_ext.h, csrc/flash_attn_m16x_ext.hip) -- header, export, argument
+checks before any device access, cln_describe text, "linked == plannable" for its kernels (fa2_fwd_m16x_kernel with CAUSAL and without LSE), and the code of those kernels
 (16x16x32 MFMAs only, no spill, no scratch, no MFMA writing over its own operands). No GPU needed: hipcc cross-compiles."""
 import ctypes
 import os
@@ -12,9 +12,11 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "cln_amd_ext.h")
-SRC = os.path.join(ROOT, "cuda-learn-notes_amd", "csrc", "flash_attn_causal.hip")
+SRC = os.path.join(ROOT, "cuda-learn-notes_amd", "csrc", "flash_attn_m16x_ext.hip")
 SINGLE = " [single stage: every tile fetch waited for where it is issued]"
 sys.path.insert(0, os.path.join(ROOT, "cuda-learn-notes_amd", "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_handles import M16X, M16X_CLAIMS, kernel_handles, m16x_args  # noqa: E402
 
 
 @pytest.mark.parametrize("lang,cc", [("c", "gcc"), ("c++", "g++")])
@@ -73,29 +75,17 @@ def test_describe_names_the_causal_family(built):
             m.describe("cln_fa2_fwd_causal", dims, 2)
 
 
-def _fa2c_kernel_handles(so):
-    nm, filt = shutil.which("nm"), shutil.which("c++filt")
-    if not nm or not filt:
-        pytest.skip("binutils nm / c++filt not available")
-    out = subprocess.run([nm, so], capture_output=True, text=True, check=True).stdout
-    names = [ln.split()[2] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "VvWwDd" and "_kernel" in ln and "__device_stub__" not in ln]
-    dem = subprocess.run([filt], input="\n".join(n.replace("DF16_", "Dh") for n in names), capture_output=True, text=True, check=True).stdout
-    res = []
-    for d in dem.splitlines():
-        mm = re.match(r"(?:void )?((?:\w+::)*\w+_kernel)(?:<(.*?)>)?\(", d)
-        if mm and mm.group(1).startswith("fa2c::"):
-            res.append((mm.group(1), [a.strip() for a in (mm.group(2) or "").split(",")]))
-    return res
-
-
 def test_causal_kernels_in_the_product_library_are_exactly_the_plannable_ones(built):
     from cuda_learn_notes_amd import _loader
     linked = set()
-    for fam, a in _fa2c_kernel_handles(_loader.so_path("libcln_amd.so")):
-        assert fam == "fa2c::fa2_fwd_m16x_causal_kernel", fam
-        # <D, fragment prefetch depth, deferred key blocks, option bits (5 = phase-A priority + split prologue; + 32768 + 2 << 16: single stage), launch order>
-        assert a[1:3] == (["8", "4"] if a[0] == "64" else ["4", "4"]) and a[3] in ("5", "163845") and a[4] == "1", a
-        linked.add((int(a[0]), a[3] == "163845"))
+    for fam, a in kernel_handles(_loader.so_path("libcln_amd.so")):
+        if fam != M16X or not M16X_CLAIMS["causal"](a):
+            continue
+        # <D, rows per wave, key tile, fragment prefetch depth, deferred key blocks, option bits (5 = phase-A priority + split prologue; + 32768 + 2 << 16:
+        # single stage), V as [B,H,N,D], CAUSAL, launch order (1: heaviest first), no LSE>
+        assert a[1:3] == ["32", "128"] and a[6] == "false", a
+        assert a[3:5] == (["8", "4"] if a[0] == "64" else ["4", "4"]) and a[5] in ("5", "163845") and a[8] == "1", a
+        linked.add((int(a[0]), a[5] == "163845"))
     plannable = set()
     for D in (32, 64, 96, 128, 256):
         for (B, H) in ((1, 1), (1, 8), (4, 8), (2, 96)):
@@ -114,7 +104,7 @@ def test_causal_kernels_use_16x16x32_mfma_only_and_keep_registers(tmp_path):
     import kernel_resources as kr
     import mfma_overlap_scan as scan
     kernels, s = kr.report(SRC, keep=str(tmp_path))
-    ks = [k for k in kernels if "fa2c::fa2_fwd_m16x_causal_kernel" in k["demangled"]]
+    ks = [k for k in kernels if m16x_args(k["demangled"]) and M16X_CLAIMS["causal"](m16x_args(k["demangled"]))]
     assert len(ks) == 4, [k["demangled"] for k in kernels]
     text = open(s).read()
     for k in ks:

@@ -1,4 +1,4 @@
-"""GPU: the attention forward with log-sum-exp (fa2_fwd_lse -> cln_fa2_fwd_lse / cln_fa2_fwd_causal_lse, csrc/flash_attn_fwd_lse.hip), the
+"""GPU: the attention forward with log-sum-exp (fa2_fwd_lse -> cln_fa2_fwd_lse / cln_fa2_fwd_causal_lse, csrc/flash_attn_m16x_ext.hip), the
 backward (fa2_bwd -> cln_fa2_bwd / cln_fa2_bwd_causal, csrc/flash_attn_bwd.hip) and the autograd function fa2_attention, against fp64 CPU
 autograd of the (masked) softmax attention and torch SDPA's fp16 backward."""
 import pytest

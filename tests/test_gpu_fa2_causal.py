@@ -1,4 +1,4 @@
-"""GPU: the causal FlashAttention-2 forward (cuda_learn_notes_amd.fa2_fwd_causal -> cln_fa2_fwd_causal, csrc/flash_attn_causal.hip)
+"""GPU: the causal FlashAttention-2 forward (cuda_learn_notes_amd.fa2_fwd_causal -> cln_fa2_fwd_causal, csrc/flash_attn_m16x_ext.hip)
 against an fp64 masked softmax computed here on the CPU."""
 import pytest
 import torch

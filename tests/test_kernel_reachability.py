@@ -7,27 +7,11 @@ kernel). Reachable set: cln_describe() evaluated over a grid of (name, shape, st
 path runs (csrc/flash_attn.hip fa2_plan, csrc/hgemm.hip best_plan)."""
 import os
 import re
-import shutil
-import subprocess
-
-import pytest
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def kernel_handles(so):
-    nm, filt = shutil.which("nm"), shutil.which("c++filt")
-    if not nm or not filt:
-        pytest.skip("binutils nm / c++filt not available")
-    out = subprocess.run([nm, so], capture_output=True, text=True, check=True).stdout
-    names = [ln.split()[2] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "VvWwDd" and "_kernel" in ln and "__device_stub__" not in ln]  # template kernels: weak objects, plain kernels: data objects
-    dem = subprocess.run([filt], input="\n".join(n.replace("DF16_", "Dh") for n in names), capture_output=True, text=True, check=True).stdout
-    res = []
-    for d in dem.splitlines():
-        m = re.match(r"(?:void )?((?:\w+::)*\w+_kernel)(?:<(.*?)>)?\(", d)
-        if m:
-            res.append((m.group(1), [a.strip() for a in (m.group(2) or "").split(",")]))
-    return res
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_handles import M16X, M16X_CLAIMS, kernel_handles  # noqa: E402
 
 
 def test_attention_kernels_in_the_product_library_are_exactly_the_plannable_ones(built):
@@ -54,6 +38,9 @@ def test_attention_kernels_in_the_product_library_are_exactly_the_plannable_ones
             assert a[:2] == ["4", "2"] and a[2] in ("2", "3") and a[3] in ("0", "320", "384"), a
             linked.add(("fa2_fwd_pair2", int(a[3]) or 512, a[2] == "3"))
         elif f == "fa2_fwd_m16x_kernel":  # 6th argument: option bits (32768 = single-stage form); 7th: V given transposed ([B,H,D,N], the *_swizzle_qkv names)
+            if not M16X_CLAIMS["plain"](a):  # the causal and the LSE forms: test_fa2_causal_surface.py, test_fa2_bwd_surface.py
+                continue
+            assert a[8] == "0", a  # launch order: 1 (heaviest row blocks first) iff causal
             # the shipped options: phase-A priority + split prologue (1 << 18: fp32-scaled scores; 1 << 19: row sums on the matrix pipe, with them at 32 rows per wave)
             assert int(a[5]) & ~(32768 | (3 << 16) | (1 << 18) | (1 << 19)) == 5, a
             assert bool(int(a[5]) & (1 << 19)) == (bool(int(a[5]) & (1 << 18)) and a[1] == "32"), a
@@ -101,6 +88,23 @@ def test_attention_kernels_in_the_product_library_are_exactly_the_plannable_ones
                             plannable.add((fam, d))
     assert linked - plannable == set(), sorted(linked - plannable)   # nothing dead in the product library
     assert plannable - linked == set(), sorted(plannable - linked)   # nothing the planner names is missing
+
+
+def test_every_m16x_forward_instantiation_is_claimed_by_exactly_one_reachability_test(built):
+    """All m16x forwards are instantiations of ONE template; the three "linked == plannable" tests share them out by CAUSAL and LSE (this module:
+    the reference names; test_fa2_causal_surface.py; test_fa2_bwd_surface.py). None may fall between them and none may be counted twice."""
+    from cuda_learn_notes_amd import _loader
+    claimed = {n: 0 for n in M16X_CLAIMS}
+    total = 0
+    for fam, a in kernel_handles(_loader.so_path("libcln_amd.so")):
+        if fam != M16X:
+            continue
+        assert len(a) == 10, a
+        who = [n for n, claims in M16X_CLAIMS.items() if claims(a)]
+        assert len(who) == 1, (a, who)
+        claimed[who[0]] += 1
+        total += 1
+    assert total == 30 and claimed == {"plain": 18, "causal": 4, "lse": 8}, (total, claimed)
 
 
 def test_one_wave_per_simd_hgemm_instantiations_are_exactly_the_plannable_ones(built):
