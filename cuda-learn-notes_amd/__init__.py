@@ -104,6 +104,16 @@ def kv_append_rope_table(max_pos, D, theta=10000.0, device=None):
     return host.kv_append_rope_table(max_pos, D, theta, device)
 
 
+def fa2_prefill_paged(q, k_pages, v_pages, block_table, seqlens, out, lse=None):
+    """Prefill attention (a prompt or a chunk of one, any T >= 1) over a paged KV cache with grouped query heads into out: the tensors and the
+    semantics of fa2_decode_paged_multi with T unbounded -- the lengths count the T newest tokens, query t sees the keys
+    j < len - (T - 1 - t), a sequence with len < T has its live tokens right-aligned as kv_append_paged writes them. One launch, no workspace.
+    D in {64, 128}, Hq / Hkv in {1, 2, 4, 8}, page in {16, ..., 256}. C entry cln_fa2_prefill_paged (include/cln_amd_ext.h). Not a reference
+    name."""
+    from . import host
+    return host.fa2_prefill_paged(q, k_pages, v_pages, block_table, seqlens, out, lse)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

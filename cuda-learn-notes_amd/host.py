@@ -889,3 +889,38 @@ def kv_append_paged(k_new, v_new, k_pages, v_pages, block_table, seqlens, q=None
     rc = fn(k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), ptr(q),
             ptr(q_out), ptr(rope_table), B, T, Hq, Hkv, P, max_pages, page, D, max_pos, mode, _stream())
     _raise("kv_append_paged", rc, "kv_append_paged: max_pages * page or B * T too large for one launch")
+
+
+def fa2_prefill_paged(q, k_pages, v_pages, block_table, seqlens, out, lse=None):
+    """Prefill attention (a prompt or a chunk of one) over a paged KV cache with grouped query heads into out; one launch, no workspace. The
+    tensors and the semantics of fa2_decode_paged_multi with any T >= 1: q, out fp16 [B,T,Hq,D]; k_pages, v_pages fp16 [P,Hkv,page,D];
+    block_table int32 [B,max_pages] and seqlens int32 [B] on the GPU (never read by the host; lengths clamped to [0, max_pages * page] by the
+    kernel; the live table entries must lie in [0, P)); lse fp32 [B,T,Hq] (natural log) or None. seqlens[b] counts the T newest tokens, whose
+    K / V rows are already in the pool (kv_append_paged); query t sees the keys j < len_b - (T - 1 - t), and a query that sees none gets O = 0
+    and LSE = -inf, so a sequence with len_b < T has its live tokens right-aligned: that is how a ragged prefill batch is expressed. D in
+    {64, 128}, Hq / Hkv in {1, 2, 4, 8}, page in {16, 32, 64, 128, 256}. Deterministic. C entry cln_fa2_prefill_paged
+    (include/cln_amd_ext.h); no CPU path."""
+    name = "fa2_prefill_paged"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 7 + [ctypes.c_int] * 8 + [ctypes.c_void_p])
+    _decode_check((q, k_pages, v_pages, out), (block_table, seqlens))
+    if q.dim() != 4 or k_pages.dim() != 4 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    B, T, Hq, D = q.shape
+    P, Hkv, page = k_pages.shape[:3]
+    max_pages = block_table.shape[1]
+    _check_shape(k_pages, P, Hkv, page, D)
+    _check_shape(v_pages, P, Hkv, page, D)
+    _check_shape(block_table, B, max_pages)
+    _check_shape(out, B, T, Hq, D)
+    _check_shape(seqlens, B)
+    if lse is not None:
+        _check_dtype(lse, torch.float32)
+        _check_dev(lse)
+        _check_shape(lse, B, T, Hq)
+    if Hq % Hkv:
+        raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
+    if D not in (64, 128) or Hq // Hkv not in _PAGED_GROUPS or page not in _PAGED_PAGES:
+        raise _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D)
+    rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), out.data_ptr(),
+            None if lse is None else lse.data_ptr(), B, T, Hq, Hkv, P, max_pages, page, D, _stream())
+    _raise(name, rc, "%s: max_pages * page or B * Hkv * ceil(T * Hq / Hkv / 128) too large for one launch" % name)

@@ -423,6 +423,20 @@ def describe_decode_paged_multi(B, T, Hq, Hkv, max_pages, page, D):
     return buf.value.decode()
 
 
+def describe_prefill_paged(B, T, Hq, Hkv, max_pages, page, D):
+    """describe() for cln_fa2_prefill_paged (include/cln_amd_ext.h): the kernel instantiation, its tile geometry and the grid as text, from
+    cln_fa2_prefill_paged_describe (no GPU needed). ValueError for an unsupported or invalid shape."""
+    import ctypes
+    from . import _loader
+    fn = _loader.load_so("libcln_amd.so").cln_fa2_prefill_paged_describe
+    fn.argtypes, fn.restype = [ctypes.c_int] * 7 + [ctypes.c_char_p, ctypes.c_int], ctypes.c_int
+    buf = ctypes.create_string_buffer(1024)
+    rc = fn(int(B), int(T), int(Hq), int(Hkv), int(max_pages), int(page), int(D), buf, 1024)
+    if rc < 0:
+        raise ValueError("cln_fa2_prefill_paged: shape %s not supported (status %d)" % ((B, T, Hq, Hkv, max_pages, page, D), rc))
+    return buf.value.decode()
+
+
 def stages_honoured(name, dims, stages=2):
     """True when `stages` selects the pipeline depth of the kernel `name` runs for `dims`, False when the plan has one pipeline and
     the value is ignored (cln_stages_honoured; the text of describe() then carries "stages ignored"). Same errors as describe()."""

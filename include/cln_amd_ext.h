@@ -139,6 +139,28 @@ int cln_kv_append_paged(const void* k_new, const void* v_new, void* k_pages, voi
                         int max_pos, int rope_mode, void* stream);
 int cln_kv_append_paged_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int rope_mode, char* buf, int len);
 
+/* ---- Prefill attention over the same PAGED KV cache: the semantics of cln_fa2_decode_paged_multi with T unbounded, for a prompt or a chunk of one
+ * that cln_kv_append_paged has written. q, o: fp16 [B,T,Hq,D]; k_pages, v_pages, block_table, seqlens as for cln_fa2_decode_paged; lse: fp32
+ * [B,T,Hq] or NULL. len_b = clamp(seqlens[b], 0, max_pages page) counts the T newest tokens, and
+ *   o[b,t,h,:] = sum_{j < n(b,t)} softmax_j(q[b,t,h,:] . K_j / sqrt(D)) V_j,   n(b,t) = len_b - (T - 1 - t);
+ * n(b,t) <= 0 gives o = 0 and lse = -inf. A sequence with len_b < T therefore has its live tokens right-aligned, exactly as cln_kv_append_paged
+ * treats it: that is how a ragged prefill batch is expressed. Scores and softmax statistics in fp32, P rounded to fp16 for the second product.
+ * Supported: any T >= 1; D in {64, 128}; G = Hq / Hkv in {1, 2, 4, 8}; page in {16, 32, 64, 128, 256}; max_pages page < 2^31. Of a sequence only
+ * the table entries 0 .. ceil(len_b / page) - 1 are read, and only the rows < len_b of the pages they name; THE LIVE ENTRIES MUST LIE IN [0, P).
+ * One launch, no workspace, no split over the keys, no atomics: a workgroup owns 128 consecutive query rows r = t G + g of a (sequence, KV head)
+ * and walks the keys below the causal edge of its last token in steps of 64, so a sequence's bits depend neither on its neighbours nor on where
+ * its pages lie. T <= 8 is also served by cln_fa2_decode_paged_multi, which splits the keys and is the entry for few rows over a long context;
+ * the two agree within tolerance, not in bits.
+ * Returns 0, -1 (a NULL q, k_pages, v_pages, block_table, seqlens or o; one of q, k_pages, v_pages, o not 16-byte aligned or block_table, seqlens,
+ * lse not 4-byte aligned; a non-positive dimension; Hq % Hkv != 0; o or lse equal to an input or to each other), -2 (other D, G or page;
+ * max_pages page >= 2^31; a grid that does not fit) -- all checked before any device access -- or -3 (launch error).
+ * cln_fa2_prefill_paged_describe writes the kernel instantiation, its tile geometry (rows= and keys=) and the grid as text into buf (at most len
+ * bytes, NUL-terminated) and returns the text's length, or the same -1 / -2.
+ */
+int cln_fa2_prefill_paged(const void* q, const void* k_pages, const void* v_pages, const int* block_table, const int* seqlens, void* o, float* lse,
+                          int B, int T, int Hq, int Hkv, int P, int max_pages, int page, int D, void* stream);
+int cln_fa2_prefill_paged_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
