@@ -114,6 +114,29 @@ def fa2_prefill_paged(q, k_pages, v_pages, block_table, seqlens, out, lse=None):
     return host.fa2_prefill_paged(q, k_pages, v_pages, block_table, seqlens, out, lse)
 
 
+def kv_append_paged_fp8(k_new, v_new, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, q=None, q_out=None, rope_table=None, rope="none"):
+    """kv_append_paged into an FP8 cache: k_pages / v_pages torch.float8_e4m3fn [P,Hkv,page,D], k_scale / v_scale fp32 [Hkv] on the GPU (a stored
+    byte c of KV head h means e4m3(c) * scale[h]); K and V are multiplied by 1 / scale in fp32, clamped to +-448 and rounded to nearest even, q is
+    rotated and written as fp16 without a scale. Everything else as kv_append_paged. C entry cln_kv_append_paged_fp8 (include/cln_amd_ext.h).
+    Not a reference name."""
+    from . import host
+    return host.kv_append_paged_fp8(k_new, v_new, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, q, q_out, rope_table, rope)
+
+
+def fa2_decode_paged_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse=None, workspace=None):
+    """fa2_decode_paged over an FP8 cache: k_pages / v_pages torch.float8_e4m3fn [P,Hkv,page,D], k_scale / v_scale fp32 [Hkv] on the GPU; q, out
+    fp16 [B,Hq,D], lse fp32 [B,Hq] or None. Everything else as fa2_decode_paged. C entry cln_fa2_decode_paged_fp8 (include/cln_amd_ext.h). Not
+    a reference name."""
+    from . import host
+    return host.fa2_decode_paged_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse, workspace)
+
+
+def fa2_decode_paged_fp8_plan(B, Hq, Hkv, max_pages, page, D):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_fp8 for this shape; depends on nothing else. C entry cln_fa2_decode_paged_fp8_plan."""
+    from . import host
+    return host.fa2_decode_paged_fp8_plan(B, Hq, Hkv, max_pages, page, D)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

@@ -924,3 +924,112 @@ def fa2_prefill_paged(q, k_pages, v_pages, block_table, seqlens, out, lse=None):
     rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), out.data_ptr(),
             None if lse is None else lse.data_ptr(), B, T, Hq, Hkv, P, max_pages, page, D, _stream())
     _raise(name, rc, "%s: max_pages * page or B * Hkv * ceil(T * Hq / Hkv / 128) too large for one launch" % name)
+
+
+def _fp8_check(k_pages, v_pages, k_scale, v_scale, Hkv):
+    """What the FP8 cache entries ask of the pools and scales: torch.float8_e4m3fn pools, fp32 [Hkv] scales, all on the GPU."""
+    for t in (k_pages, v_pages):
+        _check_dtype(t, torch.float8_e4m3fn)
+    for t in (k_scale, v_scale):
+        _check_dtype(t, torch.float32)
+    _check_dev(k_pages, v_pages, k_scale, v_scale)
+    _check_shape(k_scale, Hkv)
+    _check_shape(v_scale, Hkv)
+
+
+def fa2_decode_paged_fp8_plan(B, Hq, Hkv, max_pages, page, D):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_fp8: a function of these six numbers only (cln_fa2_decode_paged_fp8_plan,
+    include/cln_amd_ext.h); the key step is that of the FP8 kernel, so it may differ from fa2_decode_paged_plan. No GPU needed."""
+    args = (int(B), int(Hq), int(Hkv), int(max_pages), int(page), int(D))
+    rc, plan = _decode_plan("cln_fa2_decode_paged_fp8_plan", args)
+    if rc == -2:
+        raise _paged_unsupported("fa2_decode_paged_fp8", *args)
+    if rc == -1 and args[2] > 0 and args[1] % args[2]:
+        raise RuntimeError("fa2_decode_paged_fp8: %d query heads are no multiple of %d KV heads" % (args[1], args[2]))
+    _raise("fa2_decode_paged_fp8", rc)
+    return plan
+
+
+def fa2_decode_paged_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse=None, workspace=None):
+    """Single-query attention over a paged KV cache held in FP8, with grouped query heads, into out: q, out fp16 [B,Hq,D]; k_pages, v_pages
+    torch.float8_e4m3fn [P,Hkv,page,D]; k_scale, v_scale fp32 [Hkv], block_table int32 [B,max_pages] and seqlens int32 [B] on the GPU (never
+    read by the host). A stored byte c of KV head h means e4m3(c) * scale[h]; the scales must be finite and > 0 and the live bytes no NaN code
+    (the caller's contract, not checked). lse fp32 [B,Hq] (natural log) or None. Lengths, table entries, D, Hq / Hkv, page and workspace as for
+    fa2_decode_paged, with fa2_decode_paged_fp8_plan(...)[2] bytes. Deterministic. C entry cln_fa2_decode_paged_fp8 (include/cln_amd_ext.h);
+    no CPU path."""
+    name = "fa2_decode_paged_fp8"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 10 + [ctypes.c_longlong] + [ctypes.c_int] * 7 + [ctypes.c_void_p])
+    _decode_check((q, out), (block_table, seqlens))
+    if q.dim() != 3 or k_pages.dim() != 4 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    B, Hq, D = q.shape
+    P, Hkv, page = k_pages.shape[:3]
+    _fp8_check(k_pages, v_pages, k_scale, v_scale, Hkv)
+    max_pages = block_table.shape[1]
+    _check_shape(k_pages, P, Hkv, page, D)
+    _check_shape(v_pages, P, Hkv, page, D)
+    _check_shape(block_table, B, max_pages)
+    _check_shape(out, B, Hq, D)
+    _check_shape(seqlens, B)
+    lse_ptr = _decode_lse(lse, B, Hq)
+    ws_ptr, ws_bytes = _decode_workspace(name, fa2_decode_paged_fp8_plan(B, Hq, Hkv, max_pages, page, D)[2], workspace, q.device)
+    rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), k_scale.data_ptr(),
+            v_scale.data_ptr(), out.data_ptr(), lse_ptr, ws_ptr, ws_bytes, B, Hq, Hkv, P, max_pages, page, D, _stream())
+    _raise(name, rc)
+
+
+def kv_append_paged_fp8(k_new, v_new, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, q=None, q_out=None, rope_table=None, rope="none"):
+    """kv_append_paged into a cache held in FP8; one launch. k_new, v_new fp16 [B,T,Hkv,D]; k_pages, v_pages torch.float8_e4m3fn
+    [P,Hkv,page,D], written in place; k_scale, v_scale fp32 [Hkv], block_table int32 [B,max_pages] and seqlens int32 [B] on the GPU (never read
+    by the host). Positions, liveness, rope, q, q_out and rope_table are those of kv_append_paged; q is rotated and written as fp16 without a
+    scale. Every element of a live K or V row is stored as e4m3(clamp(y * (1 / scale[h]), -448, 448)), fp32 arithmetic, round to nearest even,
+    y the fp16 input or the fp32 rotation result (not rounded to fp16 in between). The scales must be finite and > 0 and the inputs finite
+    (the caller's contract, not checked). Deterministic. C entry cln_kv_append_paged_fp8 (include/cln_amd_ext.h); no CPU path."""
+    name = "kv_append_paged_fp8"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 11 + [ctypes.c_int] * 10 + [ctypes.c_void_p])
+    if rope not in _ROPE_MODES:
+        raise RuntimeError("%s: rope %r not supported ('none', 'half' or 'interleaved')" % (name, rope))
+    mode = _ROPE_MODES[rope]
+    if mode == 0 and not (q is None and q_out is None and rope_table is None):
+        raise RuntimeError("%s: rope 'none' takes no q, q_out or rope_table" % name)
+    if mode != 0 and rope_table is None:
+        raise RuntimeError("%s: rope %r needs a rope_table (kv_append_rope_table)" % (name, rope))
+    if (q is None) != (q_out is None):
+        raise RuntimeError("%s: q and q_out are given together or not at all" % name)
+    _decode_check((k_new, v_new) + ((q, q_out) if q is not None else ()), (block_table, seqlens))
+    if k_new.dim() != 4 or k_pages.dim() != 4 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    B, T, Hkv, D = k_new.shape
+    P, _, page, _ = k_pages.shape
+    _fp8_check(k_pages, v_pages, k_scale, v_scale, Hkv)
+    max_pages = block_table.shape[1]
+    _check_shape(v_new, B, T, Hkv, D)
+    _check_shape(k_pages, P, Hkv, page, D)
+    _check_shape(v_pages, P, Hkv, page, D)
+    _check_shape(block_table, B, max_pages)
+    _check_shape(seqlens, B)
+    Hq, max_pos = Hkv, 0
+    if q is not None:
+        if q.dim() != 4:
+            raise RuntimeError("Tensor size mismatch!")
+        Hq = q.shape[2]
+        _check_shape(q, B, T, Hq, D)
+        _check_shape(q_out, B, T, Hq, D)
+    if rope_table is not None:
+        _check_dtype(rope_table, torch.float32)
+        _check_dev(rope_table)
+        if rope_table.dim() != 2:
+            raise RuntimeError("Tensor size mismatch!")
+        max_pos = rope_table.shape[0]
+        _check_shape(rope_table, max_pos, D)
+    if D not in (64, 128):
+        raise RuntimeError("%s: headdim %d not supported (64 or 128)" % (name, D))
+    if page not in _PAGED_PAGES:
+        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+    if Hq % Hkv:
+        raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    rc = fn(k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(),
+            k_scale.data_ptr(), v_scale.data_ptr(), ptr(q), ptr(q_out), ptr(rope_table), B, T, Hq, Hkv, P, max_pages, page, D, max_pos, mode,
+            _stream())
+    _raise(name, rc, "%s: max_pages * page or B * T too large for one launch" % name)

@@ -161,6 +161,42 @@ int cln_fa2_prefill_paged(const void* q, const void* k_pages, const void* v_page
                           int B, int T, int Hq, int Hkv, int P, int max_pages, int page, int D, void* stream);
 int cln_fa2_prefill_paged_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len);
 
+/* ---- The same PAGED KV cache held in FP8: a quantising append (the writer) and single-query decode attention (the reader).
+ * k_pages, v_pages: one byte per element, [P,Hkv,page,D] contiguous, OCP e4m3fn (torch.float8_e4m3fn; max finite 448; NOT the fnuz encoding of
+ * gfx942). k_scale, v_scale: fp32 [Hkv], one scale per KV head, ON THE DEVICE and never read by the host (a per-tensor scale is the same value
+ * repeated). A stored byte c of KV head h means the real value e4m3(c) * scale[h]. block_table, seqlens, the page sizes, D, the liveness rules and
+ * the caller's contracts are exactly those of cln_kv_append_paged and cln_fa2_decode_paged. THE CALLER'S CONTRACT, not checked on the device: every
+ * scale is finite and > 0, the new rows are finite, and no live byte of the pools is a NaN code (0x7f, 0xff; the append never writes one).
+ *
+ * cln_kv_append_paged_fp8: cln_kv_append_paged with k_scale, v_scale behind seqlens. k_new, v_new, q, q_out are fp16 and rope_table fp32 as there;
+ * q is rotated and written as fp16 exactly as there, without a scale. For every element of a live K or V row the kernel stores, all in IEEE fp32:
+ *   inv = 1.0f / scale[h];  z = y * inv;  z clamped to [-448, 448];  the byte = z rounded to e4m3 to nearest, ties to even,
+ * where y is the fp16 input converted exactly (V, and K with rope_mode 0) or the fp32 rotation result x1 c - x2 s, x1 s + x2 c, with no rounding to
+ * fp16 in between. Values beyond 448 scale[h] saturate to +-448 scale[h]; no NaN byte is ever written. A token that is not live writes nothing to
+ * the pools and zeros to its q_out rows; a table entry outside [0, P) stores nothing. One launch, no workspace, no atomics.
+ * Returns as cln_kv_append_paged, with k_scale, v_scale among the required pointers (4-byte aligned, equal to no output).
+ *
+ * cln_fa2_decode_paged_fp8: cln_fa2_decode_paged with k_scale, v_scale behind seqlens; q, o fp16 [B,Hq,D], lse fp32 [B,Hq] or NULL:
+ *   O[b,h,:] = sum_{j < len_b} softmax_j(q[b,h] . (k8_j k_scale[h / G]) / sqrt(D)) (v8_j v_scale[h / G]),
+ * LSE the natural log of the partition sum of those scaled scores. The scales are folded out of the loop (k_scale into the score multiplier,
+ * v_scale into the workgroup's partial), so results are bit-repeatable and a sequence's bits depend neither on its neighbours nor on where its
+ * pages lie. cln_fa2_decode_paged_fp8_plan: as cln_fa2_decode_paged_plan, with the key step of the FP8 kernel (256 keys at D = 64, 128 at
+ * D = 128): *chunk is a multiple of max(page, that step), the workspace formula is the same. The plans of the fp16 and the FP8 entry may differ.
+ * Returns as cln_fa2_decode_paged, with k_scale, v_scale among the required 4-byte aligned inputs.
+ * The *_describe entries write the kernel instantiation and the launch / plan as text, as their fp16 counterparts do.
+ * Not provided: FP8 forms of cln_fa2_decode_paged_multi and cln_fa2_prefill_paged, e5m2, per-token or per-page scales, scales computed on the
+ * device, FP8 q or o.
+ */
+int cln_kv_append_paged_fp8(const void* k_new, const void* v_new, void* k_pages, void* v_pages, const int* block_table, const int* seqlens,
+                            const float* k_scale, const float* v_scale, const void* q, void* q_out, const float* rope_table, int B, int T, int Hq,
+                            int Hkv, int P, int max_pages, int page, int D, int max_pos, int rope_mode, void* stream);
+int cln_kv_append_paged_fp8_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int rope_mode, char* buf, int len);
+int cln_fa2_decode_paged_fp8_plan(int B, int Hq, int Hkv, int max_pages, int page, int D, int* splits, int* chunk, long long* workspace_bytes);
+int cln_fa2_decode_paged_fp8(const void* q, const void* k_pages, const void* v_pages, const int* block_table, const int* seqlens,
+                             const float* k_scale, const float* v_scale, void* o, float* lse, void* workspace, long long workspace_bytes, int B,
+                             int Hq, int Hkv, int P, int max_pages, int page, int D, void* stream);
+int cln_fa2_decode_paged_fp8_describe(int B, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
