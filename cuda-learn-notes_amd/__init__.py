@@ -137,6 +137,29 @@ def fa2_decode_paged_fp8_plan(B, Hq, Hkv, max_pages, page, D):
     return host.fa2_decode_paged_fp8_plan(B, Hq, Hkv, max_pages, page, D)
 
 
+def fa2_decode_paged_multi_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse=None, workspace=None):
+    """fa2_decode_paged_multi over a paged KV cache held in FP8: k_pages, v_pages torch.float8_e4m3fn [P,Hkv,page,D], k_scale, v_scale fp32
+    [Hkv] on the GPU; q, out fp16 [B,T,Hq,D], T in 1 … 8, lse fp32 [B,T,Hq] or None. Everything else as fa2_decode_paged_multi. C entry
+    cln_fa2_decode_paged_multi_fp8 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_decode_paged_multi_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse, workspace)
+
+
+def fa2_decode_paged_multi_fp8_plan(B, T, Hq, Hkv, max_pages, page, D):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_fp8 for this shape; depends on nothing else. C entry
+    cln_fa2_decode_paged_multi_fp8_plan."""
+    from . import host
+    return host.fa2_decode_paged_multi_fp8_plan(B, T, Hq, Hkv, max_pages, page, D)
+
+
+def fa2_prefill_paged_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse=None):
+    """fa2_prefill_paged over a paged KV cache held in FP8: k_pages, v_pages torch.float8_e4m3fn [P,Hkv,page,D], k_scale, v_scale fp32 [Hkv] on
+    the GPU; q, out fp16 [B,T,Hq,D], any T >= 1, lse fp32 [B,T,Hq] or None. Everything else as fa2_prefill_paged. C entry
+    cln_fa2_prefill_paged_fp8 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_prefill_paged_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

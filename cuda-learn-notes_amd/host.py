@@ -978,6 +978,73 @@ def fa2_decode_paged_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_s
     _raise(name, rc)
 
 
+def fa2_decode_paged_multi_fp8_plan(B, T, Hq, Hkv, max_pages, page, D):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_fp8: a function of these seven numbers only
+    (cln_fa2_decode_paged_multi_fp8_plan, include/cln_amd_ext.h); the key step is that of fa2_decode_paged_multi. No GPU needed."""
+    name = "fa2_decode_paged_multi_fp8"
+    args = (int(B), int(T), int(Hq), int(Hkv), int(max_pages), int(page), int(D))
+    rc, plan = _decode_plan("cln_%s_plan" % name, args)
+    if rc == -2:
+        if args[6] in (64, 128) and args[1] > 8:
+            raise RuntimeError("%s: T %d not supported (1 … 8)" % (name, args[1]))
+        raise _paged_unsupported(name, args[0], *args[2:])
+    if rc == -1 and args[3] > 0 and args[2] % args[3]:
+        raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, args[2], args[3]))
+    _raise(name, rc)
+    return plan
+
+
+def _fp8_attn_check(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse):
+    """The tensor checks the two [B,T,Hq,D] FP8 attention entries share; returns (B, T, Hq, Hkv, P, max_pages, page, D, lse pointer)."""
+    _decode_check((q, out), (block_table, seqlens))
+    if q.dim() != 4 or k_pages.dim() != 4 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    B, T, Hq, D = q.shape
+    P, Hkv, page = k_pages.shape[:3]
+    _fp8_check(k_pages, v_pages, k_scale, v_scale, Hkv)
+    max_pages = block_table.shape[1]
+    _check_shape(k_pages, P, Hkv, page, D)
+    _check_shape(v_pages, P, Hkv, page, D)
+    _check_shape(block_table, B, max_pages)
+    _check_shape(out, B, T, Hq, D)
+    _check_shape(seqlens, B)
+    return B, T, Hq, Hkv, P, max_pages, page, D, _decode_lse(lse, B, T, Hq)
+
+
+def fa2_decode_paged_multi_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse=None, workspace=None):
+    """fa2_decode_paged_multi over a paged KV cache held in FP8: q, out fp16 [B,T,Hq,D]; k_pages, v_pages torch.float8_e4m3fn [P,Hkv,page,D];
+    k_scale, v_scale fp32 [Hkv], block_table int32 [B,max_pages] and seqlens int32 [B] on the GPU (never read by the host). A stored byte c of
+    KV head h means e4m3(c) * scale[h]; the scales must be finite and > 0 and the live bytes no NaN code (the caller's contract, not checked).
+    lse fp32 [B,T,Hq] (natural log) or None. T, lengths, table entries, D, Hq / Hkv, page and workspace as for fa2_decode_paged_multi, with
+    fa2_decode_paged_multi_fp8_plan(...)[2] bytes. Deterministic. C entry cln_fa2_decode_paged_multi_fp8 (include/cln_amd_ext.h); no CPU
+    path."""
+    name = "fa2_decode_paged_multi_fp8"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 10 + [ctypes.c_longlong] + [ctypes.c_int] * 8 + [ctypes.c_void_p])
+    B, T, Hq, Hkv, P, max_pages, page, D, lse_ptr = _fp8_attn_check(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse)
+    ws_ptr, ws_bytes = _decode_workspace(name, fa2_decode_paged_multi_fp8_plan(B, T, Hq, Hkv, max_pages, page, D)[2], workspace, q.device)
+    rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), k_scale.data_ptr(),
+            v_scale.data_ptr(), out.data_ptr(), lse_ptr, ws_ptr, ws_bytes, B, T, Hq, Hkv, P, max_pages, page, D, _stream())
+    _raise(name, rc)
+
+
+def fa2_prefill_paged_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse=None):
+    """fa2_prefill_paged over a paged KV cache held in FP8; one launch, no workspace: q, out fp16 [B,T,Hq,D], any T >= 1; k_pages, v_pages
+    torch.float8_e4m3fn [P,Hkv,page,D]; k_scale, v_scale fp32 [Hkv], block_table int32 [B,max_pages] and seqlens int32 [B] on the GPU (never
+    read by the host). A stored byte c of KV head h means e4m3(c) * scale[h]; the scales must be finite and > 0 and the live bytes no NaN code
+    (the caller's contract, not checked). lse fp32 [B,T,Hq] (natural log) or None. Lengths, the right-aligned ragged batch, table entries, D,
+    Hq / Hkv and page as for fa2_prefill_paged. Deterministic. C entry cln_fa2_prefill_paged_fp8 (include/cln_amd_ext.h); no CPU path."""
+    name = "fa2_prefill_paged_fp8"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 9 + [ctypes.c_int] * 8 + [ctypes.c_void_p])
+    B, T, Hq, Hkv, P, max_pages, page, D, lse_ptr = _fp8_attn_check(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse)
+    if Hq % Hkv:
+        raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
+    if D not in (64, 128) or Hq // Hkv not in _PAGED_GROUPS or page not in _PAGED_PAGES:
+        raise _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D)
+    rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), k_scale.data_ptr(),
+            v_scale.data_ptr(), out.data_ptr(), lse_ptr, B, T, Hq, Hkv, P, max_pages, page, D, _stream())
+    _raise(name, rc, "%s: max_pages * page or B * Hkv * ceil(T * Hq / Hkv / 128) too large for one launch" % name)
+
+
 def kv_append_paged_fp8(k_new, v_new, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, q=None, q_out=None, rope_table=None, rope="none"):
     """kv_append_paged into a cache held in FP8; one launch. k_new, v_new fp16 [B,T,Hkv,D]; k_pages, v_pages torch.float8_e4m3fn
     [P,Hkv,page,D], written in place; k_scale, v_scale fp32 [Hkv], block_table int32 [B,max_pages] and seqlens int32 [B] on the GPU (never read

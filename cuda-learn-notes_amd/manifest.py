@@ -499,3 +499,31 @@ def describe_decode_paged_fp8(B, Hq, Hkv, max_pages, page, D):
     if rc < 0:
         raise ValueError("cln_fa2_decode_paged_fp8: shape %s not supported (status %d)" % ((B, Hq, Hkv, max_pages, page, D), rc))
     return buf.value.decode()
+
+
+def describe_decode_paged_multi_fp8(B, T, Hq, Hkv, max_pages, page, D):
+    """describe() for cln_fa2_decode_paged_multi_fp8 (include/cln_amd_ext.h): the kernel instantiations and the split plan as text, from
+    cln_fa2_decode_paged_multi_fp8_describe (no GPU needed). ValueError for an unsupported or invalid shape."""
+    import ctypes
+    from . import _loader
+    fn = _loader.load_so("libcln_amd.so").cln_fa2_decode_paged_multi_fp8_describe
+    fn.argtypes, fn.restype = [ctypes.c_int] * 7 + [ctypes.c_char_p, ctypes.c_int], ctypes.c_int
+    buf = ctypes.create_string_buffer(1280)
+    rc = fn(int(B), int(T), int(Hq), int(Hkv), int(max_pages), int(page), int(D), buf, 1280)
+    if rc < 0:
+        raise ValueError("cln_fa2_decode_paged_multi_fp8: shape %s not supported (status %d)" % ((B, T, Hq, Hkv, max_pages, page, D), rc))
+    return buf.value.decode()
+
+
+def describe_prefill_paged_fp8(B, T, Hq, Hkv, max_pages, page, D):
+    """describe() for cln_fa2_prefill_paged_fp8 (include/cln_amd_ext.h): the kernel instantiation, its tile geometry and the grid as text, from
+    cln_fa2_prefill_paged_fp8_describe (no GPU needed). ValueError for an unsupported or invalid shape."""
+    import ctypes
+    from . import _loader
+    fn = _loader.load_so("libcln_amd.so").cln_fa2_prefill_paged_fp8_describe
+    fn.argtypes, fn.restype = [ctypes.c_int] * 7 + [ctypes.c_char_p, ctypes.c_int], ctypes.c_int
+    buf = ctypes.create_string_buffer(1280)
+    rc = fn(int(B), int(T), int(Hq), int(Hkv), int(max_pages), int(page), int(D), buf, 1280)
+    if rc < 0:
+        raise ValueError("cln_fa2_prefill_paged_fp8: shape %s not supported (status %d)" % ((B, T, Hq, Hkv, max_pages, page, D), rc))
+    return buf.value.decode()

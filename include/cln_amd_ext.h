@@ -184,8 +184,7 @@ int cln_fa2_prefill_paged_describe(int B, int T, int Hq, int Hkv, int max_pages,
  * D = 128): *chunk is a multiple of max(page, that step), the workspace formula is the same. The plans of the fp16 and the FP8 entry may differ.
  * Returns as cln_fa2_decode_paged, with k_scale, v_scale among the required 4-byte aligned inputs.
  * The *_describe entries write the kernel instantiation and the launch / plan as text, as their fp16 counterparts do.
- * Not provided: FP8 forms of cln_fa2_decode_paged_multi and cln_fa2_prefill_paged, e5m2, per-token or per-page scales, scales computed on the
- * device, FP8 q or o.
+ * Not provided: e5m2, per-token or per-page scales, scales computed on the device, FP8 q or o.
  */
 int cln_kv_append_paged_fp8(const void* k_new, const void* v_new, void* k_pages, void* v_pages, const int* block_table, const int* seqlens,
                             const float* k_scale, const float* v_scale, const void* q, void* q_out, const float* rope_table, int B, int T, int Hq,
@@ -196,6 +195,30 @@ int cln_fa2_decode_paged_fp8(const void* q, const void* k_pages, const void* v_p
                              const float* k_scale, const float* v_scale, void* o, float* lse, void* workspace, long long workspace_bytes, int B,
                              int Hq, int Hkv, int P, int max_pages, int page, int D, void* stream);
 int cln_fa2_decode_paged_fp8_describe(int B, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len);
+
+/* ---- The other two readers of the FP8 cache: multi-token decode (T <= 8) and prefill (any T) attention on the matrix cores.
+ * cln_fa2_decode_paged_multi_fp8 is cln_fa2_decode_paged_multi and cln_fa2_prefill_paged_fp8 is cln_fa2_prefill_paged with the pools, the scales
+ * and the caller's contract of the section above (k_scale, v_scale behind seqlens): q, o fp16 [B,T,Hq,D], lse fp32 [B,T,Hq] or NULL,
+ *   O[b,t,h,:] = sum_{j < n(b,t)} softmax_j(q[b,t,h] . (k8_j k_scale[h / G]) / sqrt(D)) (v8_j v_scale[h / G]),   n(b,t) = len_b - (T - 1 - t),
+ * LSE the natural log of the partition sum of those scaled scores, n(b,t) <= 0: O = 0 and LSE = -inf; len_b, the right-aligned ragged batch,
+ * D, G, page and the limits as for the fp16 entries. The kernels are the fp16 ones reading bytes: every element is converted to fp16 once
+ * (exactly: every e4m3 value is an fp16 value) and both products run on v_mfma_f32_16x16x32_f16 over the unscaled codes; k_scale enters the fp32
+ * score multiplier and v_scale the normalisation (the workgroup's partial with a split plan). The pools are inputs and are not written.
+ * Deterministic; a sequence's bits depend neither on its neighbours nor on where its pages lie.
+ * cln_fa2_decode_paged_multi_fp8_plan: the plan of cln_fa2_decode_paged_multi (the same 128-key step, the same workspace formula), a function of
+ * its arguments alone. Returns as the fp16 entries, with k_scale, v_scale among the required inputs (4-byte aligned, equal to no output).
+ * The *_describe entries write the kernel instantiation and the plan / grid as text, as their fp16 counterparts do.
+ */
+int cln_fa2_decode_paged_multi_fp8_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int* splits, int* chunk,
+                                        long long* workspace_bytes);
+int cln_fa2_decode_paged_multi_fp8(const void* q, const void* k_pages, const void* v_pages, const int* block_table, const int* seqlens,
+                                   const float* k_scale, const float* v_scale, void* o, float* lse, void* workspace, long long workspace_bytes,
+                                   int B, int T, int Hq, int Hkv, int P, int max_pages, int page, int D, void* stream);
+int cln_fa2_decode_paged_multi_fp8_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len);
+int cln_fa2_prefill_paged_fp8(const void* q, const void* k_pages, const void* v_pages, const int* block_table, const int* seqlens,
+                              const float* k_scale, const float* v_scale, void* o, float* lse, int B, int T, int Hq, int Hkv, int P, int max_pages,
+                              int page, int D, void* stream);
+int cln_fa2_prefill_paged_fp8_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len);
 
 #ifdef __cplusplus
 }
