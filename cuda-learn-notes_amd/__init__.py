@@ -160,6 +160,24 @@ def fa2_prefill_paged_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_
     return host.fa2_prefill_paged_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse)
 
 
+def fa2_prefill_paged_varlen(q, k_pages, v_pages, block_table, seqlens, cu_q, out, lse=None):
+    """fa2_prefill_paged for a packed batch with a per-sequence number of new tokens: q, out fp16 [total_q,Hq,D], lse fp32 [total_q,Hq] or None,
+    cu_q int32 [B+1] on the GPU (never read by the host): the tokens of sequence b are the packed rows cu_q[b] .. cu_q[b+1]-1, T_b of them, and
+    seqlens[b] counts them. Rows outside [cu_q[0], cu_q[B]) are not touched. A sequence's bits are those of fa2_prefill_paged on it alone. One
+    launch, no workspace. C entry cln_fa2_prefill_paged_varlen (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_prefill_paged_varlen(q, k_pages, v_pages, block_table, seqlens, cu_q, out, lse)
+
+
+def kv_append_paged_varlen(k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q=None, q_out=None, rope_table=None, rope="none"):
+    """kv_append_paged for a packed batch with a per-sequence number of new tokens: k_new, v_new fp16 [total_q,Hkv,D], q / q_out fp16
+    [total_q,Hq,D] or None, cu_q int32 [B+1] on the GPU as for fa2_prefill_paged_varlen; token i of sequence b stands at
+    seqlens[b] - T_b + i. Everything else as kv_append_paged. One launch, nothing read on the host. C entry cln_kv_append_paged_varlen
+    (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.kv_append_paged_varlen(k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q, q_out, rope_table, rope)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

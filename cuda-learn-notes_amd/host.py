@@ -926,6 +926,96 @@ def fa2_prefill_paged(q, k_pages, v_pages, block_table, seqlens, out, lse=None):
     _raise(name, rc, "%s: max_pages * page or B * Hkv * ceil(T * Hq / Hkv / 128) too large for one launch" % name)
 
 
+def fa2_prefill_paged_varlen(q, k_pages, v_pages, block_table, seqlens, cu_q, out, lse=None):
+    """fa2_prefill_paged for a packed batch with a per-sequence number of new tokens; one launch, no workspace. q, out fp16 [total_q,Hq,D]; lse
+    fp32 [total_q,Hq] (natural log) or None; cu_q int32 [B+1] on the GPU, non-decreasing with 0 <= cu_q[0] and cu_q[B] <= total_q (never read by
+    the host: the grid comes from B and total_q): the tokens of sequence b are the packed rows cu_q[b] .. cu_q[b+1]-1, T_b of them (0 is
+    allowed). k_pages, v_pages, block_table [B,max_pages] and seqlens [B] as for fa2_prefill_paged; seqlens[b] counts the T_b newest tokens,
+    token i sees the keys j < len_b - (T_b - 1 - i), and a query that sees none gets O = 0 and LSE = -inf. Packed rows outside
+    [cu_q[0], cu_q[B]) are neither read nor written. A sequence's bits are those of fa2_prefill_paged on that sequence alone. D in {64, 128},
+    Hq / Hkv in {1, 2, 4, 8}, page in {16, 32, 64, 128, 256}. Deterministic. C entry cln_fa2_prefill_paged_varlen (include/cln_amd_ext.h); no
+    CPU path."""
+    name = "fa2_prefill_paged_varlen"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 8 + [ctypes.c_int] * 8 + [ctypes.c_void_p])
+    _decode_check((q, k_pages, v_pages, out), (block_table, seqlens, cu_q))
+    if q.dim() != 3 or k_pages.dim() != 4 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    total_q, Hq, D = q.shape
+    P, Hkv, page = k_pages.shape[:3]
+    B, max_pages = block_table.shape
+    _check_shape(k_pages, P, Hkv, page, D)
+    _check_shape(v_pages, P, Hkv, page, D)
+    _check_shape(out, total_q, Hq, D)
+    _check_shape(seqlens, B)
+    _check_shape(cu_q, B + 1)
+    if lse is not None:
+        _check_dtype(lse, torch.float32)
+        _check_dev(lse)
+        _check_shape(lse, total_q, Hq)
+    if Hq % Hkv:
+        raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
+    if D not in (64, 128) or Hq // Hkv not in _PAGED_GROUPS or page not in _PAGED_PAGES:
+        raise _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D)
+    rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), cu_q.data_ptr(), out.data_ptr(),
+            None if lse is None else lse.data_ptr(), B, total_q, Hq, Hkv, P, max_pages, page, D, _stream())
+    _raise(name, rc, "%s: max_pages * page or Hkv * (total_q * Hq / Hkv / 128 + B) too large for one launch" % name)
+
+
+def kv_append_paged_varlen(k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q=None, q_out=None, rope_table=None, rope="none"):
+    """kv_append_paged for a packed batch with a per-sequence number of new tokens; one launch. k_new, v_new fp16 [total_q,Hkv,D]; q, q_out fp16
+    [total_q,Hq,D], given together or both None (q_out may be q); cu_q int32 [B+1] on the GPU as for fa2_prefill_paged_varlen (never read by
+    the host). Token i of sequence b is packed row cu_q[b] + i and stands at pos = seqlens[b] - T_b + i; liveness, rope, rope_table, the pools,
+    the table and the caller's contract are those of kv_append_paged. Packed rows outside [cu_q[0], cu_q[B]) are neither read nor written.
+    Deterministic. C entry cln_kv_append_paged_varlen (include/cln_amd_ext.h); no CPU path."""
+    name = "kv_append_paged_varlen"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 10 + [ctypes.c_int] * 10 + [ctypes.c_void_p])
+    if rope not in _ROPE_MODES:
+        raise RuntimeError("%s: rope %r not supported ('none', 'half' or 'interleaved')" % (name, rope))
+    mode = _ROPE_MODES[rope]
+    if mode == 0 and not (q is None and q_out is None and rope_table is None):
+        raise RuntimeError("%s: rope 'none' takes no q, q_out or rope_table" % name)
+    if mode != 0 and rope_table is None:
+        raise RuntimeError("%s: rope %r needs a rope_table (kv_append_rope_table)" % (name, rope))
+    if (q is None) != (q_out is None):
+        raise RuntimeError("%s: q and q_out are given together or not at all" % name)
+    halves = (k_new, v_new, k_pages, v_pages) + ((q, q_out) if q is not None else ())
+    _decode_check(halves, (block_table, seqlens, cu_q))
+    if k_new.dim() != 3 or k_pages.dim() != 4 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    total_q, Hkv, D = k_new.shape
+    P, _, page, _ = k_pages.shape
+    B, max_pages = block_table.shape
+    _check_shape(v_new, total_q, Hkv, D)
+    _check_shape(k_pages, P, Hkv, page, D)
+    _check_shape(v_pages, P, Hkv, page, D)
+    _check_shape(seqlens, B)
+    _check_shape(cu_q, B + 1)
+    Hq, max_pos = Hkv, 0
+    if q is not None:
+        if q.dim() != 3:
+            raise RuntimeError("Tensor size mismatch!")
+        Hq = q.shape[1]
+        _check_shape(q, total_q, Hq, D)
+        _check_shape(q_out, total_q, Hq, D)
+    if rope_table is not None:
+        _check_dtype(rope_table, torch.float32)
+        _check_dev(rope_table)
+        if rope_table.dim() != 2:
+            raise RuntimeError("Tensor size mismatch!")
+        max_pos = rope_table.shape[0]
+        _check_shape(rope_table, max_pos, D)
+    if D not in (64, 128):
+        raise RuntimeError("%s: headdim %d not supported (64 or 128)" % (name, D))
+    if page not in _PAGED_PAGES:
+        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+    if Hq % Hkv:
+        raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    rc = fn(k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(),
+            cu_q.data_ptr(), ptr(q), ptr(q_out), ptr(rope_table), B, total_q, Hq, Hkv, P, max_pages, page, D, max_pos, mode, _stream())
+    _raise(name, rc, "%s: max_pages * page or total_q too large for one launch" % name)
+
+
 def _fp8_check(k_pages, v_pages, k_scale, v_scale, Hkv):
     """What the FP8 cache entries ask of the pools and scales: torch.float8_e4m3fn pools, fp32 [Hkv] scales, all on the GPU."""
     for t in (k_pages, v_pages):

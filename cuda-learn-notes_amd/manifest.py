@@ -527,3 +527,35 @@ def describe_prefill_paged_fp8(B, T, Hq, Hkv, max_pages, page, D):
     if rc < 0:
         raise ValueError("cln_fa2_prefill_paged_fp8: shape %s not supported (status %d)" % ((B, T, Hq, Hkv, max_pages, page, D), rc))
     return buf.value.decode()
+
+
+def describe_prefill_paged_varlen(B, total_q, Hq, Hkv, max_pages, page, D):
+    """describe() for cln_fa2_prefill_paged_varlen (include/cln_amd_ext.h): the kernel instantiation, its tile geometry, the slots per KV head and
+    the grid as text, from cln_fa2_prefill_paged_varlen_describe (no GPU needed). ValueError for an unsupported or invalid shape."""
+    import ctypes
+    from . import _loader
+    fn = _loader.load_so("libcln_amd.so").cln_fa2_prefill_paged_varlen_describe
+    fn.argtypes, fn.restype = [ctypes.c_int] * 7 + [ctypes.c_char_p, ctypes.c_int], ctypes.c_int
+    buf = ctypes.create_string_buffer(1280)
+    rc = fn(int(B), int(total_q), int(Hq), int(Hkv), int(max_pages), int(page), int(D), buf, 1280)
+    if rc < 0:
+        raise ValueError("cln_fa2_prefill_paged_varlen: shape %s not supported (status %d)" % ((B, total_q, Hq, Hkv, max_pages, page, D), rc))
+    return buf.value.decode()
+
+
+def describe_kv_append_paged_varlen(B, total_q, Hq, Hkv, max_pages, page, D, rope_mode):
+    """describe() for cln_kv_append_paged_varlen (include/cln_amd_ext.h): the kernel instantiation and the launch as text, from
+    cln_kv_append_paged_varlen_describe (no GPU needed). rope_mode: 0 / "none", 1 / "half", 2 / "interleaved". ValueError for an unsupported or
+    invalid shape."""
+    import ctypes
+    from . import _loader
+    mode = {"none": 0, "half": 1, "interleaved": 2}.get(rope_mode, rope_mode)
+    if not isinstance(mode, int):
+        raise ValueError("cln_kv_append_paged_varlen: rope %r not supported" % (rope_mode,))
+    fn = _loader.load_so("libcln_amd.so").cln_kv_append_paged_varlen_describe
+    fn.argtypes, fn.restype = [ctypes.c_int] * 8 + [ctypes.c_char_p, ctypes.c_int], ctypes.c_int
+    buf = ctypes.create_string_buffer(1024)
+    rc = fn(int(B), int(total_q), int(Hq), int(Hkv), int(max_pages), int(page), int(D), mode, buf, 1024)
+    if rc < 0:
+        raise ValueError("cln_kv_append_paged_varlen: shape %s not supported (status %d)" % ((B, total_q, Hq, Hkv, max_pages, page, D, rope_mode), rc))
+    return buf.value.decode()

@@ -220,6 +220,37 @@ int cln_fa2_prefill_paged_fp8(const void* q, const void* k_pages, const void* v_
                               int page, int D, void* stream);
 int cln_fa2_prefill_paged_fp8_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len);
 
+/* ---- The fp16 PAGED KV cache with a PACKED batch: a per-sequence number of new tokens (the cu_seqlens_q convention of varlen attention).
+ * cln_fa2_prefill_paged_varlen is cln_fa2_prefill_paged and cln_kv_append_paged_varlen is cln_kv_append_paged with T replaced per sequence by
+ * T_b = cu_q[b+1] - cu_q[b]: q, o (k_new, v_new, q_out) are [total_q,H,D], and the tokens of sequence b are the packed rows cu_q[b] .. cu_q[b+1]-1.
+ * cu_q: int32 [B+1] ON THE DEVICE and never read by the host, non-decreasing, 0 <= cu_q[0], cu_q[B] <= total_q; both grids are sized from B and
+ * total_q alone. len_b = clamp(seqlens[b], 0, max_pages page) counts the T_b newest tokens; token i of sequence b stands at
+ * pos = seqlens[b] - T_b + i (64 bits) and sees the keys j < n(b,i) = len_b - (T_b - 1 - i); n <= 0 gives o = 0 and lse = -inf. The append's
+ * liveness rule, rotation, pointer rules and q_out zero fill are those of cln_kv_append_paged. T_b = 0 is allowed. PACKED ROWS BELOW cu_q[0] OR AT
+ * AND PAST cu_q[B] BELONG TO NO SEQUENCE: neither entry reads or writes them. A cu_q outside this contract gives unspecified values but touches no
+ * memory outside the tensors (offsets are clamped to [0, total_q], T_b to >= 0).
+ * q, o: fp16 [total_q,Hq,D]; lse: fp32 [total_q,Hq] or NULL; k_new, v_new: fp16 [total_q,Hkv,D]; q, q_out of the append: fp16 [total_q,Hq,D] or both
+ * NULL; every other tensor as in the fixed-T entries. Supported: D in {64, 128}; page in {16, 32, 64, 128, 256}; G = Hq / Hkv in {1, 2, 4, 8} for the
+ * attention, any multiple for the append; max_pages page < 2^31. One launch each, no workspace, no atomics, deterministic: the attention gives a
+ * sequence's tiles of 128 rows r = i G + g from the sequence's own row 0, so its bits are those of cln_fa2_prefill_paged called on that sequence
+ * alone with T = T_b, and depend neither on its neighbours nor on its place in the packed tensor.
+ * Returns 0, -1 (a NULL or misaligned pointer -- cu_q, block_table, seqlens, lse, rope_table need 4 bytes, the tensors 16; a non-positive B, total_q
+ * or other dimension; Hq % Hkv != 0; the pointer rules of rope_mode; forbidden aliasing, q_out == q stays allowed), -2 (other D, G, page or
+ * rope_mode; max_pages page >= 2^31; total_q G >= 2^31 or a grid that does not fit) -- all checked before any device access -- or -3 (launch
+ * error). The *_describe entries write the kernel, its geometry and the grid as text into buf (at most len bytes, NUL-terminated) and return the
+ * text's length, or the same -1 / -2.
+ */
+int cln_fa2_prefill_paged_varlen(const void* q, const void* k_pages, const void* v_pages, const int* block_table, const int* seqlens,
+                                 const int* cu_q, void* o, float* lse, int B, int total_q, int Hq, int Hkv, int P, int max_pages,
+                                 int page, int D, void* stream);
+int cln_fa2_prefill_paged_varlen_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len);
+int cln_kv_append_paged_varlen(const void* k_new, const void* v_new, void* k_pages, void* v_pages, const int* block_table,
+                               const int* seqlens, const int* cu_q, const void* q, void* q_out, const float* rope_table, int B,
+                               int total_q, int Hq, int Hkv, int P, int max_pages, int page, int D, int max_pos, int rope_mode,
+                               void* stream);
+int cln_kv_append_paged_varlen_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D, int rope_mode,
+                                        char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
