@@ -178,6 +178,37 @@ def kv_append_paged_varlen(k_new, v_new, k_pages, v_pages, block_table, seqlens,
     return host.kv_append_paged_varlen(k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q, q_out, rope_table, rope)
 
 
+def kv_append_paged_varlen_bf16(k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q=None, q_out=None, rope_table=None, rope="none"):
+    """kv_append_paged_varlen on torch.bfloat16 tensors (new rows, q, q_out, pools; rope_table stays fp32): fp32 rotation from the bf16 inputs,
+    one rounding to bf16, V and rope "none" rows copied bit for bit. Everything else as kv_append_paged_varlen; a fixed T is
+    cu_q = T * arange(B + 1). C entry cln_kv_append_paged_varlen_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.kv_append_paged_varlen_bf16(k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q, q_out, rope_table, rope)
+
+
+def fa2_prefill_paged_varlen_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, out, lse=None):
+    """fa2_prefill_paged_varlen on torch.bfloat16 tensors (q, out, pools; lse stays fp32): bf16 operands on the matrix cores, fp32 scores and
+    accumulators, P and O rounded once to bf16, nothing through fp16. Everything else as fa2_prefill_paged_varlen. C entry
+    cln_fa2_prefill_paged_varlen_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_prefill_paged_varlen_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, out, lse)
+
+
+def fa2_decode_paged_multi_bf16(q, k_pages, v_pages, block_table, seqlens, out, lse=None, workspace=None):
+    """fa2_decode_paged_multi on torch.bfloat16 tensors (q, out [B,T,Hq,D], pools; lse and the workspace stay fp32), T in 1 … 8, split over the
+    keys by fa2_decode_paged_multi_bf16_plan. Everything else as fa2_decode_paged_multi. C entry cln_fa2_decode_paged_multi_bf16
+    (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_decode_paged_multi_bf16(q, k_pages, v_pages, block_table, seqlens, out, lse, workspace)
+
+
+def fa2_decode_paged_multi_bf16_plan(B, T, Hq, Hkv, max_pages, page, D):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_bf16: what fa2_decode_paged_multi_plan returns for the same numbers. C entry
+    cln_fa2_decode_paged_multi_bf16_plan."""
+    from . import host
+    return host.fa2_decode_paged_multi_bf16_plan(B, T, Hq, Hkv, max_pages, page, D)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

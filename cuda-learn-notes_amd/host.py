@@ -671,10 +671,10 @@ def _decode_plan(cname, dims):
     return rc, (s.value, c.value, w.value)
 
 
-def _decode_check(f16, i32):
-    """The dtype and device checks the decode entries share: fp16 tensors, int32 tensors, all on the GPU."""
+def _decode_check(f16, i32, dtype=torch.float16):
+    """The dtype and device checks the decode entries share: fp16 (or, for the *_bf16 entries, bf16) tensors, int32 tensors, all on the GPU."""
     for t in f16:
-        _check_dtype(t, torch.float16)
+        _check_dtype(t, dtype)
     for t in i32:
         _check_dtype(t, torch.int32)
     _check_dev(*f16, *i32)
@@ -749,10 +749,11 @@ def _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D):
     return RuntimeError("%s: max_pages * page or B * Hkv * splits too large for one launch" % name)
 
 
-def _paged_decode(name, plan, q_dims, q, k_pages, v_pages, block_table, seqlens, out, lse, workspace):
-    """The body of fa2_decode_paged (q, out [B,Hq,D]) and fa2_decode_paged_multi ([B,T,Hq,D]): q_dims = 3 or 4, plan = the entry's *_plan."""
+def _paged_decode(name, plan, q_dims, q, k_pages, v_pages, block_table, seqlens, out, lse, workspace, dtype=torch.float16):
+    """The body of fa2_decode_paged (q, out [B,Hq,D]) and fa2_decode_paged_multi[_bf16] ([B,T,Hq,D]): q_dims = 3 or 4, plan = the entry's *_plan,
+    dtype = what q, out and the pools hold."""
     fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 8 + [ctypes.c_longlong] + [ctypes.c_int] * (q_dims + 4) + [ctypes.c_void_p])
-    _decode_check((q, k_pages, v_pages, out), (block_table, seqlens))
+    _decode_check((q, k_pages, v_pages, out), (block_table, seqlens), dtype)
     if q.dim() != q_dims or k_pages.dim() != 4 or block_table.dim() != 2:
         raise RuntimeError("Tensor size mismatch!")
     lead, D = tuple(q.shape[:-1]), q.shape[-1]  # (B, Hq) or (B, T, Hq)
@@ -793,19 +794,24 @@ def fa2_decode_paged(q, k_pages, v_pages, block_table, seqlens, out, lse=None, w
     _paged_decode("fa2_decode_paged", fa2_decode_paged_plan, 3, q, k_pages, v_pages, block_table, seqlens, out, lse, workspace)
 
 
+def _paged_multi_plan(name, B, T, Hq, Hkv, max_pages, page, D):
+    """The body of fa2_decode_paged_multi_plan and fa2_decode_paged_multi_bf16_plan: the C entry cln_<name>_plan and its error texts."""
+    args = (int(B), int(T), int(Hq), int(Hkv), int(max_pages), int(page), int(D))
+    rc, plan = _decode_plan("cln_%s_plan" % name, args)
+    if rc == -2:
+        if args[6] in (64, 128) and args[1] > 8:
+            raise RuntimeError("%s: T %d not supported (1 … 8)" % (name, args[1]))
+        raise _paged_unsupported(name, args[0], *args[2:])
+    if rc == -1 and args[3] > 0 and args[2] % args[3]:
+        raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, args[2], args[3]))
+    _raise(name, rc)
+    return plan
+
+
 def fa2_decode_paged_multi_plan(B, T, Hq, Hkv, max_pages, page, D):
     """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi: a function of these seven numbers only (cln_fa2_decode_paged_multi_plan,
     include/cln_amd_ext.h). No GPU needed."""
-    args = (int(B), int(T), int(Hq), int(Hkv), int(max_pages), int(page), int(D))
-    rc, plan = _decode_plan("cln_fa2_decode_paged_multi_plan", args)
-    if rc == -2:
-        if args[6] in (64, 128) and args[1] > 8:
-            raise RuntimeError("fa2_decode_paged_multi: T %d not supported (1 … 8)" % args[1])
-        raise _paged_unsupported("fa2_decode_paged_multi", args[0], *args[2:])
-    if rc == -1 and args[3] > 0 and args[2] % args[3]:
-        raise RuntimeError("fa2_decode_paged_multi: %d query heads are no multiple of %d KV heads" % (args[2], args[3]))
-    _raise("fa2_decode_paged_multi", rc)
-    return plan
+    return _paged_multi_plan("fa2_decode_paged_multi", B, T, Hq, Hkv, max_pages, page, D)
 
 
 def fa2_decode_paged_multi(q, k_pages, v_pages, block_table, seqlens, out, lse=None, workspace=None):
@@ -935,9 +941,13 @@ def fa2_prefill_paged_varlen(q, k_pages, v_pages, block_table, seqlens, cu_q, ou
     [cu_q[0], cu_q[B]) are neither read nor written. A sequence's bits are those of fa2_prefill_paged on that sequence alone. D in {64, 128},
     Hq / Hkv in {1, 2, 4, 8}, page in {16, 32, 64, 128, 256}. Deterministic. C entry cln_fa2_prefill_paged_varlen (include/cln_amd_ext.h); no
     CPU path."""
-    name = "fa2_prefill_paged_varlen"
+    _prefill_paged_varlen("fa2_prefill_paged_varlen", torch.float16, q, k_pages, v_pages, block_table, seqlens, cu_q, out, lse)
+
+
+def _prefill_paged_varlen(name, dtype, q, k_pages, v_pages, block_table, seqlens, cu_q, out, lse):
+    """The body of fa2_prefill_paged_varlen and fa2_prefill_paged_varlen_bf16: dtype = what q, out and the pools hold."""
     fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 8 + [ctypes.c_int] * 8 + [ctypes.c_void_p])
-    _decode_check((q, k_pages, v_pages, out), (block_table, seqlens, cu_q))
+    _decode_check((q, k_pages, v_pages, out), (block_table, seqlens, cu_q), dtype)
     if q.dim() != 3 or k_pages.dim() != 4 or block_table.dim() != 2:
         raise RuntimeError("Tensor size mismatch!")
     total_q, Hq, D = q.shape
@@ -967,7 +977,12 @@ def kv_append_paged_varlen(k_new, v_new, k_pages, v_pages, block_table, seqlens,
     the host). Token i of sequence b is packed row cu_q[b] + i and stands at pos = seqlens[b] - T_b + i; liveness, rope, rope_table, the pools,
     the table and the caller's contract are those of kv_append_paged. Packed rows outside [cu_q[0], cu_q[B]) are neither read nor written.
     Deterministic. C entry cln_kv_append_paged_varlen (include/cln_amd_ext.h); no CPU path."""
-    name = "kv_append_paged_varlen"
+    _kv_append_paged_varlen("kv_append_paged_varlen", torch.float16, k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q, q_out, rope_table,
+                            rope)
+
+
+def _kv_append_paged_varlen(name, dtype, k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q, q_out, rope_table, rope):
+    """The body of kv_append_paged_varlen and kv_append_paged_varlen_bf16: dtype = what the new rows, q, q_out and the pools hold."""
     fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 10 + [ctypes.c_int] * 10 + [ctypes.c_void_p])
     if rope not in _ROPE_MODES:
         raise RuntimeError("%s: rope %r not supported ('none', 'half' or 'interleaved')" % (name, rope))
@@ -979,7 +994,7 @@ def kv_append_paged_varlen(k_new, v_new, k_pages, v_pages, block_table, seqlens,
     if (q is None) != (q_out is None):
         raise RuntimeError("%s: q and q_out are given together or not at all" % name)
     halves = (k_new, v_new, k_pages, v_pages) + ((q, q_out) if q is not None else ())
-    _decode_check(halves, (block_table, seqlens, cu_q))
+    _decode_check(halves, (block_table, seqlens, cu_q), dtype)
     if k_new.dim() != 3 or k_pages.dim() != 4 or block_table.dim() != 2:
         raise RuntimeError("Tensor size mismatch!")
     total_q, Hkv, D = k_new.shape
@@ -1014,6 +1029,37 @@ def kv_append_paged_varlen(k_new, v_new, k_pages, v_pages, block_table, seqlens,
     rc = fn(k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(),
             cu_q.data_ptr(), ptr(q), ptr(q_out), ptr(rope_table), B, total_q, Hq, Hkv, P, max_pages, page, D, max_pos, mode, _stream())
     _raise(name, rc, "%s: max_pages * page or total_q too large for one launch" % name)
+
+
+def kv_append_paged_varlen_bf16(k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q=None, q_out=None, rope_table=None, rope="none"):
+    """kv_append_paged_varlen on bf16 tensors: k_new, v_new, q, q_out and the pools torch.bfloat16, rope_table fp32; everything else -- shapes,
+    liveness, rope, the caller's contract, the errors -- as there. The rotation runs in fp32 from the bf16 inputs with one rounding to bf16 (round
+    to nearest even); V rows and rope "none" rows are copied bit for bit. A fixed T is cu_q = T * arange(B + 1). Deterministic. C entry
+    cln_kv_append_paged_varlen_bf16 (include/cln_amd_ext.h); no CPU path."""
+    _kv_append_paged_varlen("kv_append_paged_varlen_bf16", torch.bfloat16, k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q, q_out,
+                            rope_table, rope)
+
+
+def fa2_prefill_paged_varlen_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, out, lse=None):
+    """fa2_prefill_paged_varlen on bf16 tensors: q, out and the pools torch.bfloat16, lse fp32; everything else as there. K, V and q are bf16
+    operands of the matrix cores, scores and accumulators fp32, P rounded once to bf16, O rounded once to bf16 at the store; nothing passes
+    through fp16. A fixed T is cu_q = T * arange(B + 1). Deterministic. C entry cln_fa2_prefill_paged_varlen_bf16 (include/cln_amd_ext.h); no
+    CPU path."""
+    _prefill_paged_varlen("fa2_prefill_paged_varlen_bf16", torch.bfloat16, q, k_pages, v_pages, block_table, seqlens, cu_q, out, lse)
+
+
+def fa2_decode_paged_multi_bf16_plan(B, T, Hq, Hkv, max_pages, page, D):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_bf16: what fa2_decode_paged_multi_plan returns for the same seven numbers (the
+    workspace is fp32 either way), from cln_fa2_decode_paged_multi_bf16_plan (include/cln_amd_ext.h). No GPU needed."""
+    return _paged_multi_plan("fa2_decode_paged_multi_bf16", B, T, Hq, Hkv, max_pages, page, D)
+
+
+def fa2_decode_paged_multi_bf16(q, k_pages, v_pages, block_table, seqlens, out, lse=None, workspace=None):
+    """fa2_decode_paged_multi on bf16 tensors: q, out [B,T,Hq,D] and the pools torch.bfloat16, lse and the workspace fp32; T in 1 … 8 and
+    everything else as there, with fa2_decode_paged_multi_bf16_plan(...)[2] workspace bytes. The numerics of fa2_prefill_paged_varlen_bf16; the
+    split partials and their merge are fp32. Deterministic. C entry cln_fa2_decode_paged_multi_bf16 (include/cln_amd_ext.h); no CPU path."""
+    _paged_decode("fa2_decode_paged_multi_bf16", fa2_decode_paged_multi_bf16_plan, 4, q, k_pages, v_pages, block_table, seqlens, out, lse, workspace,
+                  torch.bfloat16)
 
 
 def _fp8_check(k_pages, v_pages, k_scale, v_scale, Hkv):

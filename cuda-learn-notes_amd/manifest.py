@@ -559,3 +559,37 @@ def describe_kv_append_paged_varlen(B, total_q, Hq, Hkv, max_pages, page, D, rop
     if rc < 0:
         raise ValueError("cln_kv_append_paged_varlen: shape %s not supported (status %d)" % ((B, total_q, Hq, Hkv, max_pages, page, D, rope_mode), rc))
     return buf.value.decode()
+
+
+def _describe_bf16(cname, dims, size=1280):
+    """The text of the bf16 paged entry `cname`_describe for the int tuple dims; ValueError for an unsupported or invalid shape."""
+    import ctypes
+    from . import _loader
+    fn = getattr(_loader.load_so("libcln_amd.so"), cname + "_describe")
+    fn.argtypes, fn.restype = [ctypes.c_int] * len(dims) + [ctypes.c_char_p, ctypes.c_int], ctypes.c_int
+    buf = ctypes.create_string_buffer(size)
+    rc = fn(*dims, buf, size)
+    if rc < 0:
+        raise ValueError("%s: shape %s not supported (status %d)" % (cname, dims, rc))
+    return buf.value.decode()
+
+
+def describe_prefill_paged_varlen_bf16(B, total_q, Hq, Hkv, max_pages, page, D):
+    """describe() for cln_fa2_prefill_paged_varlen_bf16 (include/cln_amd_ext.h): the text of describe_prefill_paged_varlen with the bf16 kernel and
+    its MFMA (no GPU needed). ValueError for an unsupported or invalid shape."""
+    return _describe_bf16("cln_fa2_prefill_paged_varlen_bf16", tuple(int(x) for x in (B, total_q, Hq, Hkv, max_pages, page, D)))
+
+
+def describe_decode_paged_multi_bf16(B, T, Hq, Hkv, max_pages, page, D):
+    """describe() for cln_fa2_decode_paged_multi_bf16 (include/cln_amd_ext.h): the kernel instantiations and the split plan as text (no GPU
+    needed). ValueError for an unsupported or invalid shape."""
+    return _describe_bf16("cln_fa2_decode_paged_multi_bf16", tuple(int(x) for x in (B, T, Hq, Hkv, max_pages, page, D)))
+
+
+def describe_kv_append_paged_varlen_bf16(B, total_q, Hq, Hkv, max_pages, page, D, rope_mode):
+    """describe() for cln_kv_append_paged_varlen_bf16 (include/cln_amd_ext.h): the kernel instantiation and the launch as text (no GPU needed).
+    rope_mode: 0 / "none", 1 / "half", 2 / "interleaved". ValueError for an unsupported or invalid shape."""
+    mode = {"none": 0, "half": 1, "interleaved": 2}.get(rope_mode, rope_mode)
+    if not isinstance(mode, int):
+        raise ValueError("cln_kv_append_paged_varlen_bf16: rope %r not supported" % (rope_mode,))
+    return _describe_bf16("cln_kv_append_paged_varlen_bf16", tuple(int(x) for x in (B, total_q, Hq, Hkv, max_pages, page, D)) + (mode,))

@@ -251,6 +251,34 @@ int cln_kv_append_paged_varlen(const void* k_new, const void* v_new, void* k_pag
 int cln_kv_append_paged_varlen_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D, int rope_mode,
                                         char* buf, int len);
 
+/* ---- The PAGED KV cache in bf16: one full serving step on bf16 tensors -- append with fused RoPE, prefill of a packed
+ * batch, multi-token decode. Each entry is its fp16 namesake (cln_kv_append_paged_varlen, cln_fa2_prefill_paged_varlen,
+ * cln_fa2_decode_paged_multi[_plan|_describe]) with every fp16 tensor -- q, o, k_new, v_new, q_out, k_pages, v_pages -- in bf16 instead: the same
+ * argument lists, shapes, status codes, alignment and aliasing rules, clamping, liveness and n <= 0 -> o = 0, lse = -inf. lse, rope_table and the
+ * workspace stay fp32; cln_fa2_decode_paged_multi_bf16_plan returns what cln_fa2_decode_paged_multi_plan returns for the same seven numbers. A fixed
+ * T is cu_q = T arange(B + 1).
+ * Numerics: K, V and q are bf16 operands of v_mfma_f32_16x16x32_bf16, scores fp32 with the scale log2(e) / sqrt(D) applied to them in fp32; P is
+ * rounded once to bf16 (round to nearest even) for the P V product; accumulators, m, l, the split partials and the combine are fp32; o is rounded
+ * once to bf16 at the store. The append rotates in fp32 from the bf16 inputs with one rounding to bf16; V rows and rope_mode 0 rows are copied bit
+ * for bit. No value passes through fp16: inputs of magnitude 2^17 come through finite.
+ */
+int cln_kv_append_paged_varlen_bf16(const void* k_new, const void* v_new, void* k_pages, void* v_pages, const int* block_table,
+                                    const int* seqlens, const int* cu_q, const void* q, void* q_out, const float* rope_table, int B,
+                                    int total_q, int Hq, int Hkv, int P, int max_pages, int page, int D, int max_pos, int rope_mode,
+                                    void* stream);
+int cln_kv_append_paged_varlen_bf16_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D, int rope_mode,
+                                             char* buf, int len);
+int cln_fa2_prefill_paged_varlen_bf16(const void* q, const void* k_pages, const void* v_pages, const int* block_table, const int* seqlens,
+                                      const int* cu_q, void* o, float* lse, int B, int total_q, int Hq, int Hkv, int P, int max_pages,
+                                      int page, int D, void* stream);
+int cln_fa2_prefill_paged_varlen_bf16_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len);
+int cln_fa2_decode_paged_multi_bf16_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int* splits, int* chunk,
+                                         long long* workspace_bytes);
+int cln_fa2_decode_paged_multi_bf16(const void* q, const void* k_pages, const void* v_pages, const int* block_table, const int* seqlens,
+                                    void* o, float* lse, void* workspace, long long workspace_bytes, int B, int T, int Hq, int Hkv, int P,
+                                    int max_pages, int page, int D, void* stream);
+int cln_fa2_decode_paged_multi_bf16_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
