@@ -1,18 +1,13 @@
 // Compile unit of the FP8 paged decode attention entries cln_fa2_decode_paged_fp8_plan / cln_fa2_decode_paged_fp8 /
 // cln_fa2_decode_paged_fp8_describe (include/cln_amd_ext.h; kernels: flash_attn_decode_paged_fp8.cuh).
 #include "flash_attn_decode_paged_fp8.cuh"
+#include "paged_entry.h"
 
 namespace {
 
-// The split plan (fa2d::split_plan) with the key step of the FP8 kernel: a function of (B, Hq, Hkv, max_pages, page, D) only. A workgroup serves a
-// whole group of query heads, so the workgroup count is B Hkv S.
+// paged::decode_plan for one query token per sequence and the key step of this kernel, a function of D that is not asked of a D <= 0
 int fp8_plan(int B, int Hq, int Hkv, int max_pages, int page, int D, fa2d::PagedGeometry* g, fa2d::Plan* p) {
-  if (B <= 0 || D <= 0) return CLN_ERR_BAD_ARG;
-  const int rc = fa2d::paged_geometry(Hq, Hkv, max_pages, page, g);
-  if (rc != CLN_OK) return rc;
-  if (D != 64 && D != 128) return CLN_ERR_UNSUPPORTED;
-  const int step = fa2d::key_step_fp8(D);
-  return fa2d::split_plan((long long)B * Hkv, (long long)B * Hq, g->Nmax, page > step ? page : step, D, p);
+  return paged::decode_plan(B, 1, Hq, Hkv, max_pages, page, D, D > 0 ? fa2d::key_step_fp8(D) : 0, g, p);
 }
 
 }  // namespace
@@ -28,18 +23,14 @@ CLN_API int cln_fa2_decode_paged_fp8(const void* q, const void* k_pages, const v
                                      const float* k_scale, const float* v_scale, void* o, float* lse, void* workspace, long long workspace_bytes,
                                      int B, int Hq, int Hkv, int P, int max_pages, int page, int D, void* stream) {
   const void* in[] = {q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale};  // the last four: 4-byte aligned
-  int rc = fa2d::check_pointers(in, 7, 3, {o, lse, workspace});
-  if (rc != CLN_OK) return rc;
-  if (P <= 0) return CLN_ERR_BAD_ARG;
   fa2d::PagedGeometry g;
-  fa2d::Plan p;
-  rc = fp8_plan(B, Hq, Hkv, max_pages, page, D, &g, &p);
+  fa2d::Plan p = {};
+  const int rc = paged::decode_args(in, 7, {o, lse, workspace}, workspace_bytes, P, fp8_plan(B, Hq, Hkv, max_pages, page, D, &g, &p), p);
   if (rc != CLN_OK) return rc;
-  if (!fa2d::workspace_fits(p, workspace, workspace_bytes)) return CLN_ERR_BAD_ARG;
   const fa2d::PagedKV8 kv = {(const uint8_t*)k_pages, (const uint8_t*)v_pages, k_scale, v_scale, block_table, Hkv, max_pages, g.page_shift};
   const hipStream_t s = (hipStream_t)stream;
-  if (D == 64) return fa2d::launch_decode_paged_fp8<64>(g.group, q, kv, seqlens, o, lse, workspace, B, p.splits, p.chunk, s);
-  return fa2d::launch_decode_paged_fp8<128>(g.group, q, kv, seqlens, o, lse, workspace, B, p.splits, p.chunk, s);
+  return paged::for_head_dim(
+      D, [&](auto d) { return fa2d::launch_decode_paged_fp8<d()>(g.group, q, kv, seqlens, o, lse, workspace, B, p.splits, p.chunk, s); });
 }
 
 CLN_API int cln_fa2_decode_paged_fp8_describe(int B, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len) {

@@ -231,16 +231,4 @@ int launch_decode_paged_multi_fp8(const void* q, const fa2d::PagedKV8& kv, const
   return fa2d::launch_combine<D>(cln_check_launch(), out, seqlens, rows, T * (kv.Hkv << g_shift), kv.nmax(), S, C, stream);
 }
 
-
-// The split plan of cln_fa2_decode_paged_multi (flash_attn_decode_paged_multi.hip; the key step is the same): a function of
-// (B, T, Hq, Hkv, max_pages, page, D) only.
-inline int multi_fp8_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, fa2d::PagedGeometry* g, fa2d::Plan* p) {
-  if (B <= 0 || T <= 0 || D <= 0) return CLN_ERR_BAD_ARG;
-  const int rc = fa2d::paged_geometry(Hq, Hkv, max_pages, page, g);
-  if (rc != CLN_OK) return rc;
-  if ((D != 64 && D != 128) || T > kMaxT) return CLN_ERR_UNSUPPORTED;
-  return fa2d::split_plan((long long)B * Hkv, (long long)B * T * Hq, g->Nmax, page > kKeyStep ? page : kKeyStep, D, p);
-}
-inline int multi_fp8_tiles(int T, const fa2d::PagedGeometry& g) { return (T * g.group + 15) / 16; }
-
 }  // namespace fa2pm

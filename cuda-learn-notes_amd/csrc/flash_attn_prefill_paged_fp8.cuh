@@ -207,18 +207,4 @@ int launch_prefill_paged_fp8(const void* q, const fa2d::PagedKV8& kv, const int*
   return cln_check_launch();
 }
 
-// The checks that need no pointer, those of cln_fa2_prefill_paged (flash_attn_prefill_paged.hip): -1 for a non-positive dimension or
-// Hq % Hkv != 0, -2 for another D, G or page, max_pages page >= 2^31, T G past an int or a grid that does not fit. *tiles = the row tiles
-// (workgroups) per (sequence, KV head).
-inline int prefill_fp8_shape(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, fa2d::PagedGeometry* g, long long* tiles) {
-  if (B <= 0 || T <= 0 || D <= 0) return CLN_ERR_BAD_ARG;
-  const int rc = fa2d::paged_geometry(Hq, Hkv, max_pages, page, g);
-  if (rc != CLN_OK) return rc;
-  if (D != 64 && D != 128) return CLN_ERR_UNSUPPORTED;
-  const long long R = (long long)T * g->group;
-  *tiles = (R + kRowTile - 1) / kRowTile;
-  if (R > 0x7fffffffLL || *tiles > 0xffffffffLL / kThreads / B / Hkv) return CLN_ERR_UNSUPPORTED;
-  return CLN_OK;
-}
-
 }  // namespace fa2pp

@@ -1,32 +1,28 @@
 // Compile unit of the FP8 paged prefill attention entries cln_fa2_prefill_paged_fp8 / cln_fa2_prefill_paged_fp8_describe
 // (include/cln_amd_ext.h; kernel: flash_attn_prefill_paged_fp8.cuh).
 #include "flash_attn_prefill_paged_fp8.cuh"
+#include "paged_entry.h"
 
 CLN_API int cln_fa2_prefill_paged_fp8(const void* q, const void* k_pages, const void* v_pages, const int* block_table, const int* seqlens,
                                       const float* k_scale, const float* v_scale, void* o, float* lse, int B, int T, int Hq, int Hkv, int P,
                                       int max_pages, int page, int D, void* stream) {
   const void* const in[] = {q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale};  // 16-byte aligned up to the table, 4-byte from there on
-  for (int i = 0; i < 7; ++i)
-    if (!in[i] || !cln_aligned(in[i], i >= 3 ? 4 : 16)) return CLN_ERR_BAD_ARG;
-  if (!o || !cln_aligned16(o) || !cln_aligned(lse, 4) || (const void*)lse == o) return CLN_ERR_BAD_ARG;
-  for (int i = 0; i < 7; ++i)  // no output is an input
-    if (o == in[i] || (lse && (const void*)lse == in[i])) return CLN_ERR_BAD_ARG;
-  if (P <= 0) return CLN_ERR_BAD_ARG;
+  int rc = paged::prefill_args(in, 7, o, lse, P);
+  if (rc != CLN_OK) return rc;
   fa2d::PagedGeometry g;
   long long tiles = 0;
-  const int rc = fa2pp::prefill_fp8_shape(B, T, Hq, Hkv, max_pages, page, D, &g, &tiles);
+  rc = paged::prefill_shape(B, T, Hq, Hkv, max_pages, page, D, &g, &tiles);
   if (rc != CLN_OK) return rc;
   const fa2d::PagedKV8 kv = {(const uint8_t*)k_pages, (const uint8_t*)v_pages, k_scale, v_scale, block_table, Hkv, max_pages, g.page_shift};
   const hipStream_t s = (hipStream_t)stream;
-  return D == 64 ? fa2pp::launch_prefill_paged_fp8<64>(q, kv, seqlens, o, lse, B, T, g.g_shift, tiles, s)
-                 : fa2pp::launch_prefill_paged_fp8<128>(q, kv, seqlens, o, lse, B, T, g.g_shift, tiles, s);
+  return paged::for_head_dim(D, [&](auto d) { return fa2pp::launch_prefill_paged_fp8<d()>(q, kv, seqlens, o, lse, B, T, g.g_shift, tiles, s); });
 }
 
 CLN_API int cln_fa2_prefill_paged_fp8_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len) {
   if (!buf || len <= 0) return CLN_ERR_BAD_ARG;
   fa2d::PagedGeometry g;
   long long tiles = 0;
-  const int rc = fa2pp::prefill_fp8_shape(B, T, Hq, Hkv, max_pages, page, D, &g, &tiles);
+  const int rc = paged::prefill_shape(B, T, Hq, Hkv, max_pages, page, D, &g, &tiles);
   if (rc != CLN_OK) return rc;
   const int n = snprintf(buf, len,
                          "fa2_prefill_paged_fp8<D=%d,G=%d> T=%d page=%d rows=%d keys=%d: one launch, no workspace; %lld workgroups of 256 threads "

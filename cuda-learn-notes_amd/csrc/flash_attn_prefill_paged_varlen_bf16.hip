@@ -2,50 +2,29 @@
 // cln_fa2_prefill_paged_varlen_bf16_describe (include/cln_amd_ext.h; kernel: flash_attn_prefill_paged_varlen_bf16.cuh). The checks and the
 // status codes are those of flash_attn_prefill_paged_varlen.hip.
 #include "flash_attn_prefill_paged_varlen_bf16.cuh"
-
-namespace {
-
-// The checks that need no pointer: -1 for a non-positive dimension or Hq % Hkv != 0, -2 for another D, G or page, max_pages page >= 2^31 or a grid
-// that does not fit. *slots = the workgroups per KV head, a function of B, total_q and G alone: the offsets stay on the device.
-int varlen_shape(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D, fa2d::PagedGeometry* g, long long* slots) {
-  if (B <= 0 || total_q <= 0 || D <= 0) return CLN_ERR_BAD_ARG;
-  const int rc = fa2d::paged_geometry(Hq, Hkv, max_pages, page, g);
-  if (rc != CLN_OK) return rc;
-  if (D != 64 && D != 128) return CLN_ERR_UNSUPPORTED;
-  const long long R = (long long)total_q * g->group;
-  *slots = R / fa2b::kRowTile + B;
-  // the packed rows times G are counted in an int; the workgroups, 256 threads each, all lie in x
-  if (R > 0x7fffffffLL || *slots > 0xffffffffLL / fa2b::kThreads / Hkv) return CLN_ERR_UNSUPPORTED;
-  return CLN_OK;
-}
-
-}  // namespace
+#include "paged_entry.h"
 
 CLN_API int cln_fa2_prefill_paged_varlen_bf16(const void* q, const void* k_pages, const void* v_pages, const int* block_table, const int* seqlens,
                                               const int* cu_q, void* o, float* lse, int B, int total_q, int Hq, int Hkv, int P, int max_pages,
                                               int page, int D, void* stream) {
   const void* const in[] = {q, k_pages, v_pages, block_table, seqlens, cu_q};  // 16-byte aligned up to the table, 4-byte from there on
-  for (int i = 0; i < 6; ++i)
-    if (!in[i] || !cln_aligned(in[i], i >= 3 ? 4 : 16)) return CLN_ERR_BAD_ARG;
-  if (!o || !cln_aligned16(o) || !cln_aligned(lse, 4) || (const void*)lse == o) return CLN_ERR_BAD_ARG;
-  for (int i = 0; i < 6; ++i)  // no output is an input
-    if (o == in[i] || (lse && (const void*)lse == in[i])) return CLN_ERR_BAD_ARG;
-  if (P <= 0) return CLN_ERR_BAD_ARG;
+  int rc = paged::prefill_args(in, 6, o, lse, P);
+  if (rc != CLN_OK) return rc;
   fa2d::PagedGeometry g;
   long long slots = 0;
-  const int rc = varlen_shape(B, total_q, Hq, Hkv, max_pages, page, D, &g, &slots);
+  rc = paged::prefill_varlen_shape(B, total_q, Hq, Hkv, max_pages, page, D, &g, &slots);
   if (rc != CLN_OK) return rc;
   const fa2b::PagedKV kv = {(const bf16_t*)k_pages, (const bf16_t*)v_pages, block_table, Hkv, max_pages, g.page_shift};
   const hipStream_t s = (hipStream_t)stream;
-  return D == 64 ? fa2b::launch_prefill_paged_varlen<64>(q, kv, seqlens, cu_q, o, lse, B, total_q, g.g_shift, slots, s)
-                 : fa2b::launch_prefill_paged_varlen<128>(q, kv, seqlens, cu_q, o, lse, B, total_q, g.g_shift, slots, s);
+  return paged::for_head_dim(
+      D, [&](auto d) { return fa2b::launch_prefill_paged_varlen<d()>(q, kv, seqlens, cu_q, o, lse, B, total_q, g.g_shift, slots, s); });
 }
 
 CLN_API int cln_fa2_prefill_paged_varlen_bf16_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len) {
   if (!buf || len <= 0) return CLN_ERR_BAD_ARG;
   fa2d::PagedGeometry g;
   long long slots = 0;
-  const int rc = varlen_shape(B, total_q, Hq, Hkv, max_pages, page, D, &g, &slots);
+  const int rc = paged::prefill_varlen_shape(B, total_q, Hq, Hkv, max_pages, page, D, &g, &slots);
   if (rc != CLN_OK) return rc;
   const int n = snprintf(buf, len,
                          "fa2_prefill_paged_varlen_bf16_mfma<D=%d,G=%d> B=%d total_q=%d page=%d rows=%d keys=%d: one launch, no workspace; %lld "

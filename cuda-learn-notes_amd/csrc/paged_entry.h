@@ -1,0 +1,143 @@
+// The host side of the paged KV-cache entries (cln_kv_append_paged*, cln_fa2_prefill_paged*, cln_fa2_decode_paged*): one
+// definition of every argument check, shape check, plan and compile-time dispatch that the 13 compile units share. Host code only -- the kernels
+// are siblings, one body per element type, for the measured reason given there; nothing here can change a kernel's schedule. A unit keeps its
+// entry points, its PagedKV / Args struct and its describe text.
+#pragma once
+#include "flash_attn_decode_common.cuh"
+#include "flash_attn_decode_paged_multi.cuh"  // fa2pm::kKeyStep, kMaxT
+#include "flash_attn_prefill_paged.cuh"       // fa2pp::kRowTile
+#include "kv_append_paged.cuh"                // kva::grid_y
+#include <type_traits>
+
+namespace paged {
+
+// ---------------------------------------------------------------- compile-time dispatch
+// f(std::integral_constant<int, V>()) for the V of Vs... that v equals; the shape checks have made sure that it is one of them. A unit writes
+// its launcher once, in a generic lambda. The lists below descend because clang emits the instantiations of a generic lambda last one first: so
+// the kernels of a code object stay in ascending order, where they were when each unit spelled its switch out.
+template <int... Vs, class F>
+int pick(int v, F&& f) {
+  int rc = CLN_ERR_UNSUPPORTED;
+  (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>())), true)) || ...);
+  return rc;
+}
+template <class F>
+int for_head_dim(int D, F&& f) { return pick<128, 64>(D, f); }
+template <class F>
+int for_row_tiles(int tiles, F&& f) { return pick<4, 3, 2, 1>(tiles, f); }
+template <class F>
+int for_rope_mode(int rope_mode, F&& f) { return pick<2, 1, 0>(rope_mode, f); }
+
+// ---------------------------------------------------------------- append
+// The pointers and what goes with them. in = the n_req required inputs, then q, then rope_table; al4[i]: input i is an int32 / fp32 array,
+// 4-byte aligned, else 16-byte; out = {k_pages, v_pages, q_out}, 16-byte aligned, q_out may be null. No output is another output or an input,
+// but q_out may be q: a thread reads its pairs before it writes. rope_mode 0 takes no q, q_out or rope_table; 1 and 2 need a table, max_pos > 0
+// and q with q_out together.
+inline int append_args(const void* const* in, const int* al4, int n_req, const void* const (&out)[3], int P, int max_pos, int rope_mode) {
+  const int n_in = n_req + 2;
+  const void *q = in[n_req], *rope_table = in[n_req + 1], *q_out = out[2];
+  for (int i = 0; i < n_req; ++i)
+    if (!in[i]) return CLN_ERR_BAD_ARG;
+  if (!out[0] || !out[1]) return CLN_ERR_BAD_ARG;
+  for (int i = 0; i < n_in; ++i)
+    if (in[i] && !cln_aligned(in[i], al4[i] ? 4 : 16)) return CLN_ERR_BAD_ARG;
+  for (int i = 0; i < 3; ++i) {
+    if (!out[i]) continue;
+    if (!cln_aligned16(out[i])) return CLN_ERR_BAD_ARG;
+    for (int j = 0; j < i; ++j)
+      if (out[i] == out[j]) return CLN_ERR_BAD_ARG;
+    for (int j = 0; j < n_in; ++j)
+      if (out[i] == in[j] && !(i == 2 && j == n_req)) return CLN_ERR_BAD_ARG;
+  }
+  if (P <= 0) return CLN_ERR_BAD_ARG;
+  if (rope_mode == 0 && (q || q_out || rope_table)) return CLN_ERR_BAD_ARG;
+  if ((rope_mode == 1 || rope_mode == 2) && (!rope_table || max_pos <= 0 || (q == nullptr) != (q_out == nullptr))) return CLN_ERR_BAD_ARG;
+  return CLN_OK;
+}
+
+// The checks that need no pointer: -1 for a non-positive dimension or Hq % Hkv != 0, -2 for another D, page or rope_mode, max_pages page >= 2^31
+// or a grid that does not fit. T = the tokens per sequence, or with `packed` the packed rows total_q of all B sequences. *y = the workgroups per
+// token (a thread per 8 elements, whatever the pools hold).
+inline int append_shape(bool packed, int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int rope_mode, bool has_q, int* page_shift,
+                        long long* y) {
+  if (B <= 0 || T <= 0 || D <= 0 || Hq <= 0 || Hkv <= 0 || max_pages <= 0 || page <= 0 || Hq % Hkv != 0) return CLN_ERR_BAD_ARG;
+  if ((D != 64 && D != 128) || rope_mode < 0 || rope_mode > 2) return CLN_ERR_UNSUPPORTED;
+  fa2d::PagedGeometry g;
+  const int rc = fa2d::paged_geometry(1, 1, max_pages, page, &g);  // the page size and max_pages page; the group size is of no concern here
+  if (rc != CLN_OK) return rc;
+  *page_shift = g.page_shift;
+  *y = kva::grid_y(packed ? 1 : B, T, Hq, Hkv, has_q, D, rope_mode);
+  return *y > 0 ? CLN_OK : CLN_ERR_UNSUPPORTED;
+}
+
+// what a describe text says of the rows, by rope_mode (the FP8 entry, which never copies a row bit for bit, words mode 0 itself)
+constexpr const char* kRot[] = {"rows copied bit for bit", "K and q rotated in half-split pairs (i, i + D/2)",
+                                "K and q rotated in interleaved pairs (2i, 2i + 1)"};
+
+// ---------------------------------------------------------------- prefill
+// The pointers: n_in inputs, all required, 16-byte aligned up to the block table (index 3), 4-byte from there on; o 16-byte aligned; lse may be
+// null and is 4-byte aligned (not the 16 bytes of fa2d::check_pointers, which the decode entries use); no output is an input or the other output.
+inline int prefill_args(const void* const* in, int n_in, const void* o, const float* lse, int P) {
+  for (int i = 0; i < n_in; ++i)
+    if (!in[i] || !cln_aligned(in[i], i >= 3 ? 4 : 16)) return CLN_ERR_BAD_ARG;
+  if (!o || !cln_aligned16(o) || !cln_aligned(lse, 4) || (const void*)lse == o) return CLN_ERR_BAD_ARG;
+  for (int i = 0; i < n_in; ++i)
+    if (o == in[i] || (lse && (const void*)lse == in[i])) return CLN_ERR_BAD_ARG;
+  return P <= 0 ? CLN_ERR_BAD_ARG : CLN_OK;
+}
+
+// The checks that need no pointer: -1 for a non-positive dimension or Hq % Hkv != 0, -2 for another D, G or page, max_pages page >= 2^31, the
+// rows T G of a sequence (packed: total_q G of all of them) past an int, or a grid that does not fit: 256 threads per workgroup, all in x.
+// *tiles = the row tiles (workgroups) per (sequence, KV head) ...
+inline int prefill_shape(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, fa2d::PagedGeometry* g, long long* tiles) {
+  if (B <= 0 || T <= 0 || D <= 0) return CLN_ERR_BAD_ARG;
+  const int rc = fa2d::paged_geometry(Hq, Hkv, max_pages, page, g);
+  if (rc != CLN_OK) return rc;
+  if (D != 64 && D != 128) return CLN_ERR_UNSUPPORTED;
+  const long long R = (long long)T * g->group;
+  *tiles = (R + fa2pp::kRowTile - 1) / fa2pp::kRowTile;
+  if (R > 0x7fffffffLL || *tiles > 0xffffffffLL / fa2d::kThreads / B / Hkv) return CLN_ERR_UNSUPPORTED;
+  return CLN_OK;
+}
+// ... and for a packed batch *slots = the workgroups per KV head, the B that may stay empty included: a function of B, total_q and G alone, the
+// offsets stay on the device
+inline int prefill_varlen_shape(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D, fa2d::PagedGeometry* g, long long* slots) {
+  if (B <= 0 || total_q <= 0 || D <= 0) return CLN_ERR_BAD_ARG;
+  const int rc = fa2d::paged_geometry(Hq, Hkv, max_pages, page, g);
+  if (rc != CLN_OK) return rc;
+  if (D != 64 && D != 128) return CLN_ERR_UNSUPPORTED;
+  const long long R = (long long)total_q * g->group;
+  *slots = R / fa2pp::kRowTile + B;
+  if (R > 0x7fffffffLL || *slots > 0xffffffffLL / fa2d::kThreads / Hkv) return CLN_ERR_UNSUPPORTED;
+  return CLN_OK;
+}
+
+// ---------------------------------------------------------------- decode
+// The split plan (fa2d::split_plan) of a paged decode entry: a function of (B, T, Hq, Hkv, max_pages, page, D) and the key step of its kernel
+// only. A workgroup serves all T G query rows of a (sequence, KV head, split), so the workgroup count is B Hkv S whatever T is.
+inline int decode_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int key_step, fa2d::PagedGeometry* g, fa2d::Plan* p) {
+  if (B <= 0 || T <= 0 || D <= 0) return CLN_ERR_BAD_ARG;
+  const int rc = fa2d::paged_geometry(Hq, Hkv, max_pages, page, g);
+  if (rc != CLN_OK) return rc;
+  if ((D != 64 && D != 128) || T > fa2pm::kMaxT) return CLN_ERR_UNSUPPORTED;
+  return fa2d::split_plan((long long)B * Hkv, (long long)B * T * Hq, g->Nmax, page > key_step ? page : key_step, D, p);
+}
+// ... of the multi-token entries, whatever their pools hold: the key step of the three kernels is one number
+inline int multi_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, fa2d::PagedGeometry* g, fa2d::Plan* p) {
+  return decode_plan(B, T, Hq, Hkv, max_pages, page, D, fa2pm::kKeyStep, g, p);
+}
+// the 16-row MFMA tiles of the T G query rows of a KV head: 1 ... 4, as T <= 8 and G <= 8
+inline int multi_tiles(int T, const fa2d::PagedGeometry& g) { return (T * g.group + 15) / 16; }
+
+// The arguments of a decode entry in the order of their status codes: the pointers (fa2d::check_pointers), P, the status of the entry's plan
+// and, where the plan splits the keys, the workspace.
+inline int decode_args(const void* const* in, int n_in, const void* const (&out)[3], long long workspace_bytes, int P, int plan_rc,
+                       const fa2d::Plan& p) {
+  const int rc = fa2d::check_pointers(in, n_in, 3, out);
+  if (rc != CLN_OK) return rc;
+  if (P <= 0) return CLN_ERR_BAD_ARG;
+  if (plan_rc != CLN_OK) return plan_rc;
+  return fa2d::workspace_fits(p, out[2], workspace_bytes) ? CLN_OK : CLN_ERR_BAD_ARG;
+}
+
+}  // namespace paged

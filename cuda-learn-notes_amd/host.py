@@ -736,6 +736,7 @@ def fa2_decode(q, k_cache, v_cache, seqlens, out, lse=None, workspace=None):
 
 
 _PAGED_GROUPS, _PAGED_PAGES = (1, 2, 4, 8), (16, 32, 64, 128, 256)
+_ROPE_MODES = {"none": 0, "half": 1, "interleaved": 2}
 
 
 def _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D):
@@ -749,39 +750,142 @@ def _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D):
     return RuntimeError("%s: max_pages * page or B * Hkv * splits too large for one launch" % name)
 
 
-def _paged_decode(name, plan, q_dims, q, k_pages, v_pages, block_table, seqlens, out, lse, workspace, dtype=torch.float16):
-    """The body of fa2_decode_paged (q, out [B,Hq,D]) and fa2_decode_paged_multi[_bf16] ([B,T,Hq,D]): q_dims = 3 or 4, plan = the entry's *_plan,
-    dtype = what q, out and the pools hold."""
-    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 8 + [ctypes.c_longlong] + [ctypes.c_int] * (q_dims + 4) + [ctypes.c_void_p])
-    _decode_check((q, k_pages, v_pages, out), (block_table, seqlens), dtype)
+def _fp8_check(k_pages, v_pages, k_scale, v_scale, Hkv):
+    """What the FP8 cache entries ask of the pools and scales: torch.float8_e4m3fn pools, fp32 [Hkv] scales, all on the GPU."""
+    for t in (k_pages, v_pages):
+        _check_dtype(t, torch.float8_e4m3fn)
+    for t in (k_scale, v_scale):
+        _check_dtype(t, torch.float32)
+    _check_dev(k_pages, v_pages, k_scale, v_scale)
+    _check_shape(k_scale, Hkv)
+    _check_shape(v_scale, Hkv)
+
+
+def _paged_plan(name, *dims):
+    """The body of the paged *_plan wrappers: the C entry cln_<name>_plan for dims = (B, Hq, Hkv, max_pages, page, D), or with a T behind B
+    for the multi-token entries, and its error texts."""
+    args = tuple(map(int, dims))
+    rc, plan = _decode_plan("cln_%s_plan" % name, args)
+    Hq, Hkv, max_pages, page, D = args[-5:]
+    if rc == -2:
+        if len(args) == 7 and D in (64, 128) and args[1] > 8:
+            raise RuntimeError("%s: T %d not supported (1 … 8)" % (name, args[1]))
+        raise _paged_unsupported(name, args[0], Hq, Hkv, max_pages, page, D)
+    if rc == -1 and Hkv > 0 and Hq % Hkv:
+        raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
+    _raise(name, rc)
+    return plan
+
+
+def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, out, lse, workspace):
+    """The body of every attention entry over a paged cache. q, out: dtype [B,Hq,D] (q_dims = 3) or [B,T,Hq,D] (4), or with cu_q the packed
+    [total_q,Hq,D]; the pools hold dtype, or with k_scale / v_scale e4m3; plan = the *_plan of a decode entry, which splits the keys and takes
+    a workspace, or None for a prefill entry: one launch, and what cannot be launched is told here, in the words of the plan."""
+    packed, fp8 = cu_q is not None, k_scale is not None
+    fn = _lse_fns.get("cln_" + name) or _ext_fn(  # the prototype is put together on the first call only
+        "cln_" + name, [ctypes.c_void_p] * (7 + packed + 2 * fp8) + ([ctypes.c_void_p, ctypes.c_longlong] if plan else [])
+        + [ctypes.c_int] * (q_dims + 4 + packed) + [ctypes.c_void_p])
+    _decode_check((q, out) if fp8 else (q, k_pages, v_pages, out), (block_table, seqlens, cu_q) if packed else (block_table, seqlens), dtype)
     if q.dim() != q_dims or k_pages.dim() != 4 or block_table.dim() != 2:
         raise RuntimeError("Tensor size mismatch!")
-    lead, D = tuple(q.shape[:-1]), q.shape[-1]  # (B, Hq) or (B, T, Hq)
-    P, Hkv, page = k_pages.shape[:3]
-    max_pages = block_table.shape[1]
+    *lead, D = q.shape  # lead = [B, Hq], [B, T, Hq] or [total_q, Hq]
+    P, Hkv, page, _ = k_pages.shape
+    if fp8:
+        _fp8_check(k_pages, v_pages, k_scale, v_scale, Hkv)
+    B, max_pages = block_table.shape
     _check_shape(k_pages, P, Hkv, page, D)
     _check_shape(v_pages, P, Hkv, page, D)
-    _check_shape(block_table, lead[0], max_pages)
-    _check_shape(out, *q.shape)
-    _check_shape(seqlens, lead[0])
-    lse_ptr = _decode_lse(lse, *lead)
-    ws_ptr, ws_bytes = _decode_workspace(name, plan(*lead, Hkv, max_pages, page, D)[2], workspace, q.device)
-    rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), out.data_ptr(), lse_ptr, ws_ptr,
-            ws_bytes, *lead, Hkv, P, max_pages, page, D, _stream())
-    _raise(name, rc)
+    if not packed and B != lead[0]:
+        raise RuntimeError("Tensor size mismatch!")
+    _check_shape(out, *lead, D)
+    _check_shape(seqlens, B)
+    if packed:
+        _check_shape(cu_q, B + 1)
+    if lse is not None:
+        _check_dtype(lse, torch.float32)
+        _check_dev(lse)
+        _check_shape(lse, *lead)
+    if plan:
+        ws, too_large = _decode_workspace(name, plan(*lead, Hkv, max_pages, page, D)[2], workspace, q.device), None
+    else:
+        Hq = lead[-1]
+        if Hq % Hkv:
+            raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
+        if D not in (64, 128) or Hq // Hkv not in _PAGED_GROUPS or page not in _PAGED_PAGES:
+            raise _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D)
+        ws = ()
+        too_large = ("%s: max_pages * page or Hkv * (total_q * Hq / Hkv / 128 + B) too large for one launch" if packed else
+                     "%s: max_pages * page or B * Hkv * ceil(T * Hq / Hkv / 128) too large for one launch") % name
+    more = (cu_q.data_ptr(),) if packed else (k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ()
+    rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), *more, out.data_ptr(),
+            None if lse is None else lse.data_ptr(), *ws, *((B, *lead) if packed else lead), Hkv, P, max_pages, page, D, _stream())
+    _raise(name, rc, too_large)
+
+
+def _kv_append_paged(name, dtype, k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, q, q_out, rope_table, rope):
+    """The body of every append entry. k_new, v_new: dtype [B,T,Hkv,D], or with cu_q the packed [total_q,Hkv,D]; q, q_out alike with Hq heads;
+    the pools hold dtype, or with k_scale / v_scale e4m3."""
+    packed, fp8 = cu_q is not None, k_scale is not None
+    fn = _lse_fns.get("cln_" + name) or _ext_fn(  # the prototype is put together on the first call only
+        "cln_" + name, [ctypes.c_void_p] * (9 + packed + 2 * fp8) + [ctypes.c_int] * 10 + [ctypes.c_void_p])
+    if rope not in _ROPE_MODES:
+        raise RuntimeError("%s: rope %r not supported ('none', 'half' or 'interleaved')" % (name, rope))
+    mode = _ROPE_MODES[rope]
+    if mode == 0 and not (q is None and q_out is None and rope_table is None):
+        raise RuntimeError("%s: rope 'none' takes no q, q_out or rope_table" % name)
+    if mode != 0 and rope_table is None:
+        raise RuntimeError("%s: rope %r needs a rope_table (kv_append_rope_table)" % (name, rope))
+    if (q is None) != (q_out is None):
+        raise RuntimeError("%s: q and q_out are given together or not at all" % name)
+    rows = ((k_new, v_new) if fp8 else (k_new, v_new, k_pages, v_pages)) + ((q, q_out) if q is not None else ())
+    _decode_check(rows, (block_table, seqlens, cu_q) if packed else (block_table, seqlens), dtype)
+    if k_new.dim() != (3 if packed else 4) or k_pages.dim() != 4 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    *lead, Hkv, D = k_new.shape  # lead = [B, T] or [total_q]
+    P, _, page, _ = k_pages.shape
+    if fp8:
+        _fp8_check(k_pages, v_pages, k_scale, v_scale, Hkv)
+    B, max_pages = block_table.shape
+    _check_shape(v_new, *lead, Hkv, D)
+    _check_shape(k_pages, P, Hkv, page, D)
+    _check_shape(v_pages, P, Hkv, page, D)
+    if not packed and B != lead[0]:
+        raise RuntimeError("Tensor size mismatch!")
+    _check_shape(seqlens, B)
+    if packed:
+        _check_shape(cu_q, B + 1)
+    Hq, max_pos = Hkv, 0
+    if q is not None:
+        if q.dim() != k_new.dim():
+            raise RuntimeError("Tensor size mismatch!")
+        Hq = q.shape[-2]
+        _check_shape(q, *lead, Hq, D)
+        _check_shape(q_out, *lead, Hq, D)
+    if rope_table is not None:
+        _check_dtype(rope_table, torch.float32)
+        _check_dev(rope_table)
+        if rope_table.dim() != 2:
+            raise RuntimeError("Tensor size mismatch!")
+        max_pos = rope_table.shape[0]
+        _check_shape(rope_table, max_pos, D)
+    if D not in (64, 128):
+        raise RuntimeError("%s: headdim %d not supported (64 or 128)" % (name, D))
+    if page not in _PAGED_PAGES:
+        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+    if Hq % Hkv:
+        raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    more = (cu_q.data_ptr(),) if packed else (k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ()
+    rc = fn(k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), *more, ptr(q),
+            ptr(q_out), ptr(rope_table), *((B, *lead) if packed else lead), Hq, Hkv, P, max_pages, page, D, max_pos, mode, _stream())
+    _raise(name, rc, ("%s: max_pages * page or total_q too large for one launch" if packed else
+                      "%s: max_pages * page or B * T too large for one launch") % name)
 
 
 def fa2_decode_paged_plan(B, Hq, Hkv, max_pages, page, D):
     """(splits, chunk, workspace_bytes) of fa2_decode_paged: a function of these six numbers only (cln_fa2_decode_paged_plan,
     include/cln_amd_ext.h). No GPU needed."""
-    args = (int(B), int(Hq), int(Hkv), int(max_pages), int(page), int(D))
-    rc, plan = _decode_plan("cln_fa2_decode_paged_plan", args)
-    if rc == -2:
-        raise _paged_unsupported("fa2_decode_paged", *args)
-    if rc == -1 and args[2] > 0 and args[1] % args[2]:
-        raise RuntimeError("fa2_decode_paged: %d query heads are no multiple of %d KV heads" % (args[1], args[2]))
-    _raise("fa2_decode_paged", rc)
-    return plan
+    return _paged_plan("fa2_decode_paged", B, Hq, Hkv, max_pages, page, D)
 
 
 def fa2_decode_paged(q, k_pages, v_pages, block_table, seqlens, out, lse=None, workspace=None):
@@ -791,27 +895,15 @@ def fa2_decode_paged(q, k_pages, v_pages, block_table, seqlens, out, lse=None, w
     Hq / Hkv in {1, 2, 4, 8}, page in {16, 32, 64, 128, 256}. workspace: any contiguous GPU tensor of at least fa2_decode_paged_plan(...)[2]
     bytes; allocated here on the current stream when None and the plan splits the keys. Deterministic. C entry cln_fa2_decode_paged
     (include/cln_amd_ext.h); no CPU path."""
-    _paged_decode("fa2_decode_paged", fa2_decode_paged_plan, 3, q, k_pages, v_pages, block_table, seqlens, out, lse, workspace)
-
-
-def _paged_multi_plan(name, B, T, Hq, Hkv, max_pages, page, D):
-    """The body of fa2_decode_paged_multi_plan and fa2_decode_paged_multi_bf16_plan: the C entry cln_<name>_plan and its error texts."""
-    args = (int(B), int(T), int(Hq), int(Hkv), int(max_pages), int(page), int(D))
-    rc, plan = _decode_plan("cln_%s_plan" % name, args)
-    if rc == -2:
-        if args[6] in (64, 128) and args[1] > 8:
-            raise RuntimeError("%s: T %d not supported (1 … 8)" % (name, args[1]))
-        raise _paged_unsupported(name, args[0], *args[2:])
-    if rc == -1 and args[3] > 0 and args[2] % args[3]:
-        raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, args[2], args[3]))
-    _raise(name, rc)
-    return plan
+    _paged_attention("fa2_decode_paged", torch.float16, 3, fa2_decode_paged_plan, q, k_pages, v_pages, block_table, seqlens, None, None, None, out,
+                     lse,
+                     workspace)
 
 
 def fa2_decode_paged_multi_plan(B, T, Hq, Hkv, max_pages, page, D):
     """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi: a function of these seven numbers only (cln_fa2_decode_paged_multi_plan,
     include/cln_amd_ext.h). No GPU needed."""
-    return _paged_multi_plan("fa2_decode_paged_multi", B, T, Hq, Hkv, max_pages, page, D)
+    return _paged_plan("fa2_decode_paged_multi", B, T, Hq, Hkv, max_pages, page, D)
 
 
 def fa2_decode_paged_multi(q, k_pages, v_pages, block_table, seqlens, out, lse=None, workspace=None):
@@ -822,10 +914,9 @@ def fa2_decode_paged_multi(q, k_pages, v_pages, block_table, seqlens, out, lse=N
     a query that sees none gets O = 0 and LSE = -inf. T in 1 … 8, D in {64, 128}, Hq / Hkv in {1, 2, 4, 8}, page in {16, 32, 64, 128, 256}.
     workspace: any contiguous GPU tensor of at least fa2_decode_paged_multi_plan(...)[2] bytes; allocated here on the current stream when None
     and the plan splits the keys. Deterministic. C entry cln_fa2_decode_paged_multi (include/cln_amd_ext.h); no CPU path."""
-    _paged_decode("fa2_decode_paged_multi", fa2_decode_paged_multi_plan, 4, q, k_pages, v_pages, block_table, seqlens, out, lse, workspace)
-
-
-_ROPE_MODES = {"none": 0, "half": 1, "interleaved": 2}
+    _paged_attention("fa2_decode_paged_multi", torch.float16, 4, fa2_decode_paged_multi_plan, q, k_pages, v_pages, block_table, seqlens, None, None,
+                     None,
+                     out, lse, workspace)
 
 
 def kv_append_rope_table(max_pos, D, theta=10000.0, device=None):
@@ -849,52 +940,8 @@ def kv_append_paged(k_new, v_new, k_pages, v_pages, block_table, seqlens, q=None
     rotated in fp32 by rope_table fp32 [max_pos, D] (kv_append_rope_table) with one rounding; V is never rotated. q, q_out fp16 [B,T,Hq,D],
     given together or both None; q_out may be q. The live table entries must lie in [0, P) and name distinct pages. D in {64, 128}, page in
     {16, 32, 64, 128, 256}, Hq a multiple of Hkv, any T. Deterministic. C entry cln_kv_append_paged (include/cln_amd_ext.h); no CPU path."""
-    fn = _ext_fn("cln_kv_append_paged", [ctypes.c_void_p] * 9 + [ctypes.c_int] * 10 + [ctypes.c_void_p])
-    if rope not in _ROPE_MODES:
-        raise RuntimeError("kv_append_paged: rope %r not supported ('none', 'half' or 'interleaved')" % (rope,))
-    mode = _ROPE_MODES[rope]
-    if mode == 0 and not (q is None and q_out is None and rope_table is None):
-        raise RuntimeError("kv_append_paged: rope 'none' takes no q, q_out or rope_table")
-    if mode != 0 and rope_table is None:
-        raise RuntimeError("kv_append_paged: rope %r needs a rope_table (kv_append_rope_table)" % (rope,))
-    if (q is None) != (q_out is None):
-        raise RuntimeError("kv_append_paged: q and q_out are given together or not at all")
-    halves = (k_new, v_new, k_pages, v_pages) + ((q, q_out) if q is not None else ())
-    _decode_check(halves, (block_table, seqlens))
-    if k_new.dim() != 4 or k_pages.dim() != 4 or block_table.dim() != 2:
-        raise RuntimeError("Tensor size mismatch!")
-    B, T, Hkv, D = k_new.shape
-    P, _, page, _ = k_pages.shape
-    max_pages = block_table.shape[1]
-    _check_shape(v_new, B, T, Hkv, D)
-    _check_shape(k_pages, P, Hkv, page, D)
-    _check_shape(v_pages, P, Hkv, page, D)
-    _check_shape(block_table, B, max_pages)
-    _check_shape(seqlens, B)
-    Hq, max_pos = Hkv, 0
-    if q is not None:
-        if q.dim() != 4:
-            raise RuntimeError("Tensor size mismatch!")
-        Hq = q.shape[2]
-        _check_shape(q, B, T, Hq, D)
-        _check_shape(q_out, B, T, Hq, D)
-    if rope_table is not None:
-        _check_dtype(rope_table, torch.float32)
-        _check_dev(rope_table)
-        if rope_table.dim() != 2:
-            raise RuntimeError("Tensor size mismatch!")
-        max_pos = rope_table.shape[0]
-        _check_shape(rope_table, max_pos, D)
-    if D not in (64, 128):
-        raise RuntimeError("kv_append_paged: headdim %d not supported (64 or 128)" % D)
-    if page not in _PAGED_PAGES:
-        raise RuntimeError("kv_append_paged: page size %d not supported (16, 32, 64, 128 or 256)" % page)
-    if Hq % Hkv:
-        raise RuntimeError("kv_append_paged: %d query heads are no multiple of %d KV heads" % (Hq, Hkv))
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    rc = fn(k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), ptr(q),
-            ptr(q_out), ptr(rope_table), B, T, Hq, Hkv, P, max_pages, page, D, max_pos, mode, _stream())
-    _raise("kv_append_paged", rc, "kv_append_paged: max_pages * page or B * T too large for one launch")
+    _kv_append_paged("kv_append_paged", torch.float16, k_new, v_new, k_pages, v_pages, block_table, seqlens, None, None, None, q, q_out, rope_table,
+                     rope)
 
 
 def fa2_prefill_paged(q, k_pages, v_pages, block_table, seqlens, out, lse=None):
@@ -906,30 +953,7 @@ def fa2_prefill_paged(q, k_pages, v_pages, block_table, seqlens, out, lse=None):
     and LSE = -inf, so a sequence with len_b < T has its live tokens right-aligned: that is how a ragged prefill batch is expressed. D in
     {64, 128}, Hq / Hkv in {1, 2, 4, 8}, page in {16, 32, 64, 128, 256}. Deterministic. C entry cln_fa2_prefill_paged
     (include/cln_amd_ext.h); no CPU path."""
-    name = "fa2_prefill_paged"
-    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 7 + [ctypes.c_int] * 8 + [ctypes.c_void_p])
-    _decode_check((q, k_pages, v_pages, out), (block_table, seqlens))
-    if q.dim() != 4 or k_pages.dim() != 4 or block_table.dim() != 2:
-        raise RuntimeError("Tensor size mismatch!")
-    B, T, Hq, D = q.shape
-    P, Hkv, page = k_pages.shape[:3]
-    max_pages = block_table.shape[1]
-    _check_shape(k_pages, P, Hkv, page, D)
-    _check_shape(v_pages, P, Hkv, page, D)
-    _check_shape(block_table, B, max_pages)
-    _check_shape(out, B, T, Hq, D)
-    _check_shape(seqlens, B)
-    if lse is not None:
-        _check_dtype(lse, torch.float32)
-        _check_dev(lse)
-        _check_shape(lse, B, T, Hq)
-    if Hq % Hkv:
-        raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
-    if D not in (64, 128) or Hq // Hkv not in _PAGED_GROUPS or page not in _PAGED_PAGES:
-        raise _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D)
-    rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), out.data_ptr(),
-            None if lse is None else lse.data_ptr(), B, T, Hq, Hkv, P, max_pages, page, D, _stream())
-    _raise(name, rc, "%s: max_pages * page or B * Hkv * ceil(T * Hq / Hkv / 128) too large for one launch" % name)
+    _paged_attention("fa2_prefill_paged", torch.float16, 4, None, q, k_pages, v_pages, block_table, seqlens, None, None, None, out, lse, None)
 
 
 def fa2_prefill_paged_varlen(q, k_pages, v_pages, block_table, seqlens, cu_q, out, lse=None):
@@ -941,34 +965,7 @@ def fa2_prefill_paged_varlen(q, k_pages, v_pages, block_table, seqlens, cu_q, ou
     [cu_q[0], cu_q[B]) are neither read nor written. A sequence's bits are those of fa2_prefill_paged on that sequence alone. D in {64, 128},
     Hq / Hkv in {1, 2, 4, 8}, page in {16, 32, 64, 128, 256}. Deterministic. C entry cln_fa2_prefill_paged_varlen (include/cln_amd_ext.h); no
     CPU path."""
-    _prefill_paged_varlen("fa2_prefill_paged_varlen", torch.float16, q, k_pages, v_pages, block_table, seqlens, cu_q, out, lse)
-
-
-def _prefill_paged_varlen(name, dtype, q, k_pages, v_pages, block_table, seqlens, cu_q, out, lse):
-    """The body of fa2_prefill_paged_varlen and fa2_prefill_paged_varlen_bf16: dtype = what q, out and the pools hold."""
-    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 8 + [ctypes.c_int] * 8 + [ctypes.c_void_p])
-    _decode_check((q, k_pages, v_pages, out), (block_table, seqlens, cu_q), dtype)
-    if q.dim() != 3 or k_pages.dim() != 4 or block_table.dim() != 2:
-        raise RuntimeError("Tensor size mismatch!")
-    total_q, Hq, D = q.shape
-    P, Hkv, page = k_pages.shape[:3]
-    B, max_pages = block_table.shape
-    _check_shape(k_pages, P, Hkv, page, D)
-    _check_shape(v_pages, P, Hkv, page, D)
-    _check_shape(out, total_q, Hq, D)
-    _check_shape(seqlens, B)
-    _check_shape(cu_q, B + 1)
-    if lse is not None:
-        _check_dtype(lse, torch.float32)
-        _check_dev(lse)
-        _check_shape(lse, total_q, Hq)
-    if Hq % Hkv:
-        raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
-    if D not in (64, 128) or Hq // Hkv not in _PAGED_GROUPS or page not in _PAGED_PAGES:
-        raise _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D)
-    rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), cu_q.data_ptr(), out.data_ptr(),
-            None if lse is None else lse.data_ptr(), B, total_q, Hq, Hkv, P, max_pages, page, D, _stream())
-    _raise(name, rc, "%s: max_pages * page or Hkv * (total_q * Hq / Hkv / 128 + B) too large for one launch" % name)
+    _paged_attention("fa2_prefill_paged_varlen", torch.float16, 3, None, q, k_pages, v_pages, block_table, seqlens, cu_q, None, None, out, lse, None)
 
 
 def kv_append_paged_varlen(k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q=None, q_out=None, rope_table=None, rope="none"):
@@ -977,58 +974,9 @@ def kv_append_paged_varlen(k_new, v_new, k_pages, v_pages, block_table, seqlens,
     the host). Token i of sequence b is packed row cu_q[b] + i and stands at pos = seqlens[b] - T_b + i; liveness, rope, rope_table, the pools,
     the table and the caller's contract are those of kv_append_paged. Packed rows outside [cu_q[0], cu_q[B]) are neither read nor written.
     Deterministic. C entry cln_kv_append_paged_varlen (include/cln_amd_ext.h); no CPU path."""
-    _kv_append_paged_varlen("kv_append_paged_varlen", torch.float16, k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q, q_out, rope_table,
-                            rope)
-
-
-def _kv_append_paged_varlen(name, dtype, k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q, q_out, rope_table, rope):
-    """The body of kv_append_paged_varlen and kv_append_paged_varlen_bf16: dtype = what the new rows, q, q_out and the pools hold."""
-    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 10 + [ctypes.c_int] * 10 + [ctypes.c_void_p])
-    if rope not in _ROPE_MODES:
-        raise RuntimeError("%s: rope %r not supported ('none', 'half' or 'interleaved')" % (name, rope))
-    mode = _ROPE_MODES[rope]
-    if mode == 0 and not (q is None and q_out is None and rope_table is None):
-        raise RuntimeError("%s: rope 'none' takes no q, q_out or rope_table" % name)
-    if mode != 0 and rope_table is None:
-        raise RuntimeError("%s: rope %r needs a rope_table (kv_append_rope_table)" % (name, rope))
-    if (q is None) != (q_out is None):
-        raise RuntimeError("%s: q and q_out are given together or not at all" % name)
-    halves = (k_new, v_new, k_pages, v_pages) + ((q, q_out) if q is not None else ())
-    _decode_check(halves, (block_table, seqlens, cu_q), dtype)
-    if k_new.dim() != 3 or k_pages.dim() != 4 or block_table.dim() != 2:
-        raise RuntimeError("Tensor size mismatch!")
-    total_q, Hkv, D = k_new.shape
-    P, _, page, _ = k_pages.shape
-    B, max_pages = block_table.shape
-    _check_shape(v_new, total_q, Hkv, D)
-    _check_shape(k_pages, P, Hkv, page, D)
-    _check_shape(v_pages, P, Hkv, page, D)
-    _check_shape(seqlens, B)
-    _check_shape(cu_q, B + 1)
-    Hq, max_pos = Hkv, 0
-    if q is not None:
-        if q.dim() != 3:
-            raise RuntimeError("Tensor size mismatch!")
-        Hq = q.shape[1]
-        _check_shape(q, total_q, Hq, D)
-        _check_shape(q_out, total_q, Hq, D)
-    if rope_table is not None:
-        _check_dtype(rope_table, torch.float32)
-        _check_dev(rope_table)
-        if rope_table.dim() != 2:
-            raise RuntimeError("Tensor size mismatch!")
-        max_pos = rope_table.shape[0]
-        _check_shape(rope_table, max_pos, D)
-    if D not in (64, 128):
-        raise RuntimeError("%s: headdim %d not supported (64 or 128)" % (name, D))
-    if page not in _PAGED_PAGES:
-        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
-    if Hq % Hkv:
-        raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    rc = fn(k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(),
-            cu_q.data_ptr(), ptr(q), ptr(q_out), ptr(rope_table), B, total_q, Hq, Hkv, P, max_pages, page, D, max_pos, mode, _stream())
-    _raise(name, rc, "%s: max_pages * page or total_q too large for one launch" % name)
+    _kv_append_paged("kv_append_paged_varlen", torch.float16, k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, None, None, q, q_out,
+                     rope_table,
+                     rope)
 
 
 def kv_append_paged_varlen_bf16(k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q=None, q_out=None, rope_table=None, rope="none"):
@@ -1036,8 +984,8 @@ def kv_append_paged_varlen_bf16(k_new, v_new, k_pages, v_pages, block_table, seq
     liveness, rope, the caller's contract, the errors -- as there. The rotation runs in fp32 from the bf16 inputs with one rounding to bf16 (round
     to nearest even); V rows and rope "none" rows are copied bit for bit. A fixed T is cu_q = T * arange(B + 1). Deterministic. C entry
     cln_kv_append_paged_varlen_bf16 (include/cln_amd_ext.h); no CPU path."""
-    _kv_append_paged_varlen("kv_append_paged_varlen_bf16", torch.bfloat16, k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q, q_out,
-                            rope_table, rope)
+    _kv_append_paged("kv_append_paged_varlen_bf16", torch.bfloat16, k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, None, None, q, q_out,
+                     rope_table, rope)
 
 
 def fa2_prefill_paged_varlen_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, out, lse=None):
@@ -1045,45 +993,29 @@ def fa2_prefill_paged_varlen_bf16(q, k_pages, v_pages, block_table, seqlens, cu_
     operands of the matrix cores, scores and accumulators fp32, P rounded once to bf16, O rounded once to bf16 at the store; nothing passes
     through fp16. A fixed T is cu_q = T * arange(B + 1). Deterministic. C entry cln_fa2_prefill_paged_varlen_bf16 (include/cln_amd_ext.h); no
     CPU path."""
-    _prefill_paged_varlen("fa2_prefill_paged_varlen_bf16", torch.bfloat16, q, k_pages, v_pages, block_table, seqlens, cu_q, out, lse)
+    _paged_attention("fa2_prefill_paged_varlen_bf16", torch.bfloat16, 3, None, q, k_pages, v_pages, block_table, seqlens, cu_q, None, None, out, lse,
+                     None)
 
 
 def fa2_decode_paged_multi_bf16_plan(B, T, Hq, Hkv, max_pages, page, D):
     """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_bf16: what fa2_decode_paged_multi_plan returns for the same seven numbers (the
     workspace is fp32 either way), from cln_fa2_decode_paged_multi_bf16_plan (include/cln_amd_ext.h). No GPU needed."""
-    return _paged_multi_plan("fa2_decode_paged_multi_bf16", B, T, Hq, Hkv, max_pages, page, D)
+    return _paged_plan("fa2_decode_paged_multi_bf16", B, T, Hq, Hkv, max_pages, page, D)
 
 
 def fa2_decode_paged_multi_bf16(q, k_pages, v_pages, block_table, seqlens, out, lse=None, workspace=None):
     """fa2_decode_paged_multi on bf16 tensors: q, out [B,T,Hq,D] and the pools torch.bfloat16, lse and the workspace fp32; T in 1 … 8 and
     everything else as there, with fa2_decode_paged_multi_bf16_plan(...)[2] workspace bytes. The numerics of fa2_prefill_paged_varlen_bf16; the
     split partials and their merge are fp32. Deterministic. C entry cln_fa2_decode_paged_multi_bf16 (include/cln_amd_ext.h); no CPU path."""
-    _paged_decode("fa2_decode_paged_multi_bf16", fa2_decode_paged_multi_bf16_plan, 4, q, k_pages, v_pages, block_table, seqlens, out, lse, workspace,
-                  torch.bfloat16)
-
-
-def _fp8_check(k_pages, v_pages, k_scale, v_scale, Hkv):
-    """What the FP8 cache entries ask of the pools and scales: torch.float8_e4m3fn pools, fp32 [Hkv] scales, all on the GPU."""
-    for t in (k_pages, v_pages):
-        _check_dtype(t, torch.float8_e4m3fn)
-    for t in (k_scale, v_scale):
-        _check_dtype(t, torch.float32)
-    _check_dev(k_pages, v_pages, k_scale, v_scale)
-    _check_shape(k_scale, Hkv)
-    _check_shape(v_scale, Hkv)
+    _paged_attention("fa2_decode_paged_multi_bf16", torch.bfloat16, 4, fa2_decode_paged_multi_bf16_plan, q, k_pages, v_pages, block_table, seqlens,
+                     None, None,
+                     None, out, lse, workspace)
 
 
 def fa2_decode_paged_fp8_plan(B, Hq, Hkv, max_pages, page, D):
     """(splits, chunk, workspace_bytes) of fa2_decode_paged_fp8: a function of these six numbers only (cln_fa2_decode_paged_fp8_plan,
     include/cln_amd_ext.h); the key step is that of the FP8 kernel, so it may differ from fa2_decode_paged_plan. No GPU needed."""
-    args = (int(B), int(Hq), int(Hkv), int(max_pages), int(page), int(D))
-    rc, plan = _decode_plan("cln_fa2_decode_paged_fp8_plan", args)
-    if rc == -2:
-        raise _paged_unsupported("fa2_decode_paged_fp8", *args)
-    if rc == -1 and args[2] > 0 and args[1] % args[2]:
-        raise RuntimeError("fa2_decode_paged_fp8: %d query heads are no multiple of %d KV heads" % (args[1], args[2]))
-    _raise("fa2_decode_paged_fp8", rc)
-    return plan
+    return _paged_plan("fa2_decode_paged_fp8", B, Hq, Hkv, max_pages, page, D)
 
 
 def fa2_decode_paged_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse=None, workspace=None):
@@ -1093,58 +1025,15 @@ def fa2_decode_paged_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_s
     (the caller's contract, not checked). lse fp32 [B,Hq] (natural log) or None. Lengths, table entries, D, Hq / Hkv, page and workspace as for
     fa2_decode_paged, with fa2_decode_paged_fp8_plan(...)[2] bytes. Deterministic. C entry cln_fa2_decode_paged_fp8 (include/cln_amd_ext.h);
     no CPU path."""
-    name = "fa2_decode_paged_fp8"
-    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 10 + [ctypes.c_longlong] + [ctypes.c_int] * 7 + [ctypes.c_void_p])
-    _decode_check((q, out), (block_table, seqlens))
-    if q.dim() != 3 or k_pages.dim() != 4 or block_table.dim() != 2:
-        raise RuntimeError("Tensor size mismatch!")
-    B, Hq, D = q.shape
-    P, Hkv, page = k_pages.shape[:3]
-    _fp8_check(k_pages, v_pages, k_scale, v_scale, Hkv)
-    max_pages = block_table.shape[1]
-    _check_shape(k_pages, P, Hkv, page, D)
-    _check_shape(v_pages, P, Hkv, page, D)
-    _check_shape(block_table, B, max_pages)
-    _check_shape(out, B, Hq, D)
-    _check_shape(seqlens, B)
-    lse_ptr = _decode_lse(lse, B, Hq)
-    ws_ptr, ws_bytes = _decode_workspace(name, fa2_decode_paged_fp8_plan(B, Hq, Hkv, max_pages, page, D)[2], workspace, q.device)
-    rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), k_scale.data_ptr(),
-            v_scale.data_ptr(), out.data_ptr(), lse_ptr, ws_ptr, ws_bytes, B, Hq, Hkv, P, max_pages, page, D, _stream())
-    _raise(name, rc)
+    _paged_attention("fa2_decode_paged_fp8", torch.float16, 3, fa2_decode_paged_fp8_plan, q, k_pages, v_pages, block_table, seqlens, None, k_scale,
+                     v_scale, out,
+                     lse, workspace)
 
 
 def fa2_decode_paged_multi_fp8_plan(B, T, Hq, Hkv, max_pages, page, D):
     """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_fp8: a function of these seven numbers only
     (cln_fa2_decode_paged_multi_fp8_plan, include/cln_amd_ext.h); the key step is that of fa2_decode_paged_multi. No GPU needed."""
-    name = "fa2_decode_paged_multi_fp8"
-    args = (int(B), int(T), int(Hq), int(Hkv), int(max_pages), int(page), int(D))
-    rc, plan = _decode_plan("cln_%s_plan" % name, args)
-    if rc == -2:
-        if args[6] in (64, 128) and args[1] > 8:
-            raise RuntimeError("%s: T %d not supported (1 … 8)" % (name, args[1]))
-        raise _paged_unsupported(name, args[0], *args[2:])
-    if rc == -1 and args[3] > 0 and args[2] % args[3]:
-        raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, args[2], args[3]))
-    _raise(name, rc)
-    return plan
-
-
-def _fp8_attn_check(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse):
-    """The tensor checks the two [B,T,Hq,D] FP8 attention entries share; returns (B, T, Hq, Hkv, P, max_pages, page, D, lse pointer)."""
-    _decode_check((q, out), (block_table, seqlens))
-    if q.dim() != 4 or k_pages.dim() != 4 or block_table.dim() != 2:
-        raise RuntimeError("Tensor size mismatch!")
-    B, T, Hq, D = q.shape
-    P, Hkv, page = k_pages.shape[:3]
-    _fp8_check(k_pages, v_pages, k_scale, v_scale, Hkv)
-    max_pages = block_table.shape[1]
-    _check_shape(k_pages, P, Hkv, page, D)
-    _check_shape(v_pages, P, Hkv, page, D)
-    _check_shape(block_table, B, max_pages)
-    _check_shape(out, B, T, Hq, D)
-    _check_shape(seqlens, B)
-    return B, T, Hq, Hkv, P, max_pages, page, D, _decode_lse(lse, B, T, Hq)
+    return _paged_plan("fa2_decode_paged_multi_fp8", B, T, Hq, Hkv, max_pages, page, D)
 
 
 def fa2_decode_paged_multi_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse=None, workspace=None):
@@ -1154,13 +1043,9 @@ def fa2_decode_paged_multi_fp8(q, k_pages, v_pages, block_table, seqlens, k_scal
     lse fp32 [B,T,Hq] (natural log) or None. T, lengths, table entries, D, Hq / Hkv, page and workspace as for fa2_decode_paged_multi, with
     fa2_decode_paged_multi_fp8_plan(...)[2] bytes. Deterministic. C entry cln_fa2_decode_paged_multi_fp8 (include/cln_amd_ext.h); no CPU
     path."""
-    name = "fa2_decode_paged_multi_fp8"
-    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 10 + [ctypes.c_longlong] + [ctypes.c_int] * 8 + [ctypes.c_void_p])
-    B, T, Hq, Hkv, P, max_pages, page, D, lse_ptr = _fp8_attn_check(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse)
-    ws_ptr, ws_bytes = _decode_workspace(name, fa2_decode_paged_multi_fp8_plan(B, T, Hq, Hkv, max_pages, page, D)[2], workspace, q.device)
-    rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), k_scale.data_ptr(),
-            v_scale.data_ptr(), out.data_ptr(), lse_ptr, ws_ptr, ws_bytes, B, T, Hq, Hkv, P, max_pages, page, D, _stream())
-    _raise(name, rc)
+    _paged_attention("fa2_decode_paged_multi_fp8", torch.float16, 4, fa2_decode_paged_multi_fp8_plan, q, k_pages, v_pages, block_table, seqlens,
+                     None, k_scale,
+                     v_scale, out, lse, workspace)
 
 
 def fa2_prefill_paged_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse=None):
@@ -1169,16 +1054,8 @@ def fa2_prefill_paged_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_
     read by the host). A stored byte c of KV head h means e4m3(c) * scale[h]; the scales must be finite and > 0 and the live bytes no NaN code
     (the caller's contract, not checked). lse fp32 [B,T,Hq] (natural log) or None. Lengths, the right-aligned ragged batch, table entries, D,
     Hq / Hkv and page as for fa2_prefill_paged. Deterministic. C entry cln_fa2_prefill_paged_fp8 (include/cln_amd_ext.h); no CPU path."""
-    name = "fa2_prefill_paged_fp8"
-    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 9 + [ctypes.c_int] * 8 + [ctypes.c_void_p])
-    B, T, Hq, Hkv, P, max_pages, page, D, lse_ptr = _fp8_attn_check(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, out, lse)
-    if Hq % Hkv:
-        raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
-    if D not in (64, 128) or Hq // Hkv not in _PAGED_GROUPS or page not in _PAGED_PAGES:
-        raise _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D)
-    rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), k_scale.data_ptr(),
-            v_scale.data_ptr(), out.data_ptr(), lse_ptr, B, T, Hq, Hkv, P, max_pages, page, D, _stream())
-    _raise(name, rc, "%s: max_pages * page or B * Hkv * ceil(T * Hq / Hkv / 128) too large for one launch" % name)
+    _paged_attention("fa2_prefill_paged_fp8", torch.float16, 4, None, q, k_pages, v_pages, block_table, seqlens, None, k_scale, v_scale, out, lse,
+                     None)
 
 
 def kv_append_paged_fp8(k_new, v_new, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, q=None, q_out=None, rope_table=None, rope="none"):
@@ -1188,51 +1065,6 @@ def kv_append_paged_fp8(k_new, v_new, k_pages, v_pages, block_table, seqlens, k_
     scale. Every element of a live K or V row is stored as e4m3(clamp(y * (1 / scale[h]), -448, 448)), fp32 arithmetic, round to nearest even,
     y the fp16 input or the fp32 rotation result (not rounded to fp16 in between). The scales must be finite and > 0 and the inputs finite
     (the caller's contract, not checked). Deterministic. C entry cln_kv_append_paged_fp8 (include/cln_amd_ext.h); no CPU path."""
-    name = "kv_append_paged_fp8"
-    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 11 + [ctypes.c_int] * 10 + [ctypes.c_void_p])
-    if rope not in _ROPE_MODES:
-        raise RuntimeError("%s: rope %r not supported ('none', 'half' or 'interleaved')" % (name, rope))
-    mode = _ROPE_MODES[rope]
-    if mode == 0 and not (q is None and q_out is None and rope_table is None):
-        raise RuntimeError("%s: rope 'none' takes no q, q_out or rope_table" % name)
-    if mode != 0 and rope_table is None:
-        raise RuntimeError("%s: rope %r needs a rope_table (kv_append_rope_table)" % (name, rope))
-    if (q is None) != (q_out is None):
-        raise RuntimeError("%s: q and q_out are given together or not at all" % name)
-    _decode_check((k_new, v_new) + ((q, q_out) if q is not None else ()), (block_table, seqlens))
-    if k_new.dim() != 4 or k_pages.dim() != 4 or block_table.dim() != 2:
-        raise RuntimeError("Tensor size mismatch!")
-    B, T, Hkv, D = k_new.shape
-    P, _, page, _ = k_pages.shape
-    _fp8_check(k_pages, v_pages, k_scale, v_scale, Hkv)
-    max_pages = block_table.shape[1]
-    _check_shape(v_new, B, T, Hkv, D)
-    _check_shape(k_pages, P, Hkv, page, D)
-    _check_shape(v_pages, P, Hkv, page, D)
-    _check_shape(block_table, B, max_pages)
-    _check_shape(seqlens, B)
-    Hq, max_pos = Hkv, 0
-    if q is not None:
-        if q.dim() != 4:
-            raise RuntimeError("Tensor size mismatch!")
-        Hq = q.shape[2]
-        _check_shape(q, B, T, Hq, D)
-        _check_shape(q_out, B, T, Hq, D)
-    if rope_table is not None:
-        _check_dtype(rope_table, torch.float32)
-        _check_dev(rope_table)
-        if rope_table.dim() != 2:
-            raise RuntimeError("Tensor size mismatch!")
-        max_pos = rope_table.shape[0]
-        _check_shape(rope_table, max_pos, D)
-    if D not in (64, 128):
-        raise RuntimeError("%s: headdim %d not supported (64 or 128)" % (name, D))
-    if page not in _PAGED_PAGES:
-        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
-    if Hq % Hkv:
-        raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    rc = fn(k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(),
-            k_scale.data_ptr(), v_scale.data_ptr(), ptr(q), ptr(q_out), ptr(rope_table), B, T, Hq, Hkv, P, max_pages, page, D, max_pos, mode,
-            _stream())
-    _raise(name, rc, "%s: max_pages * page or B * T too large for one launch" % name)
+    _kv_append_paged("kv_append_paged_fp8", torch.float16, k_new, v_new, k_pages, v_pages, block_table, seqlens, None, k_scale, v_scale, q, q_out,
+                     rope_table,
+                     rope)
