@@ -209,6 +209,31 @@ def fa2_decode_paged_multi_bf16_plan(B, T, Hq, Hkv, max_pages, page, D):
     return host.fa2_decode_paged_multi_bf16_plan(B, T, Hq, Hkv, max_pages, page, D)
 
 
+def fa2_prefill_paged_varlen_window_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, window, out, lse=None):
+    """fa2_prefill_paged_varlen_bf16 with a sliding window: the query at position p sees the keys max(0, p - window + 1) … p (HF
+    sliding_window = window). Everything else as there; with window >= max_pages * page its bits. Pages wholly below the window of a sequence's
+    first new token (aligned down to max(page, 64)) are not read, nor are their table entries. C entry
+    cln_fa2_prefill_paged_varlen_window_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_prefill_paged_varlen_window_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, window, out, lse)
+
+
+def fa2_decode_paged_multi_window_bf16(q, k_pages, v_pages, block_table, seqlens, window, out, lse=None, workspace=None):
+    """fa2_decode_paged_multi_bf16 with a sliding window (the mask of fa2_prefill_paged_varlen_window_bf16), T in 1 … 8, the window -- not
+    max_pages * page -- split over the keys by fa2_decode_paged_multi_window_bf16_plan. Pages wholly below the window of the first query
+    (aligned down to max(page, 128)) are not read, nor are their table entries. C entry cln_fa2_decode_paged_multi_window_bf16
+    (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_decode_paged_multi_window_bf16(q, k_pages, v_pages, block_table, seqlens, window, out, lse, workspace)
+
+
+def fa2_decode_paged_multi_window_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_window_bf16; with window >= max_pages * page what
+    fa2_decode_paged_multi_bf16_plan returns. C entry cln_fa2_decode_paged_multi_window_bf16_plan."""
+    from . import host
+    return host.fa2_decode_paged_multi_window_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

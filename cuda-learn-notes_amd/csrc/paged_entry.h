@@ -1,5 +1,5 @@
-// The host side of the paged KV-cache entries (cln_kv_append_paged*, cln_fa2_prefill_paged*, cln_fa2_decode_paged*; DESIGN 4.4.6, 4.4.8): one
-// definition of every argument check, shape check, plan and compile-time dispatch that the 13 compile units share. Host code only -- the kernels
+// The host side of the paged KV-cache entries (cln_kv_append_paged*, cln_fa2_prefill_paged*, cln_fa2_decode_paged*; DESIGN 4.4.6, 4.4.8, 4.4.9): one
+// definition of every argument check, shape check, plan and compile-time dispatch that the 15 compile units share. Host code only -- the kernels
 // are siblings, one body per element type, for the measured reason given there; nothing here can change a kernel's schedule. A unit keeps its
 // entry points, its PagedKV / Args struct and its describe text.
 #pragma once
@@ -125,6 +125,26 @@ inline int decode_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, i
 // ... of the multi-token entries, whatever their pools hold: the key step of the three kernels is one number
 inline int multi_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, fa2d::PagedGeometry* g, fa2d::Plan* p) {
   return decode_plan(B, T, Hq, Hkv, max_pages, page, D, fa2pm::kKeyStep, g, p);
+}
+// The sliding window of the *_window_* entries: the query at position p sees the keys max(0, p - window + 1) .. p; window >= 1.
+inline int window_arg(int window) { return window <= 0 ? CLN_ERR_BAD_ARG : CLN_OK; }
+// ... and the split plan of the windowed multi-token decode: not max_pages page but the span of keys a sequence can hold between the aligned start
+// of its window (a multiple of U = max(page, key step) at or below the lower edge of its first new token) and its length,
+//   span = min(Nmax, round_up(window + T - 1, U) + U),
+// is what the S splits of C keys divide, so S C >= span. A function of the shape and the window only; for window >= Nmax the plan of multi_plan.
+inline long long multi_window_unit(int page) { return page > fa2pm::kKeyStep ? page : fa2pm::kKeyStep; }
+inline long long multi_window_span(int T, int page, int window, long long Nmax) {
+  const long long U = multi_window_unit(page), reach = ((long long)window + T - 1 + U - 1) / U * U + U;
+  return reach < Nmax ? reach : Nmax;
+}
+inline int multi_window_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window, fa2d::PagedGeometry* g, fa2d::Plan* p) {
+  if (B <= 0 || T <= 0 || D <= 0) return CLN_ERR_BAD_ARG;
+  int rc = fa2d::paged_geometry(Hq, Hkv, max_pages, page, g);
+  if (rc != CLN_OK) return rc;
+  if ((D != 64 && D != 128) || T > fa2pm::kMaxT) return CLN_ERR_UNSUPPORTED;
+  rc = window_arg(window);
+  if (rc != CLN_OK) return rc;
+  return fa2d::split_plan((long long)B * Hkv, (long long)B * T * Hq, multi_window_span(T, page, window, g->Nmax), multi_window_unit(page), D, p);
 }
 // the 16-row MFMA tiles of the T G query rows of a KV head: 1 ... 4, as T <= 8 and G <= 8
 inline int multi_tiles(int T, const fa2d::PagedGeometry& g) { return (T * g.group + 15) / 16; }

@@ -761,11 +761,20 @@ def _fp8_check(k_pages, v_pages, k_scale, v_scale, Hkv):
     _check_shape(v_scale, Hkv)
 
 
-def _paged_plan(name, *dims):
+def _paged_window(name, window):
+    """() without a window, else the one more int of the *_window_* entries: W >= 1."""
+    if window is None:
+        return ()
+    if int(window) < 1:
+        raise RuntimeError("%s: window %d not supported (>= 1)" % (name, int(window)))
+    return (int(window),)
+
+
+def _paged_plan(name, *dims, window=None):
     """The body of the paged *_plan wrappers: the C entry cln_<name>_plan for dims = (B, Hq, Hkv, max_pages, page, D), or with a T behind B
-    for the multi-token entries, and its error texts."""
+    for the multi-token entries, and its error texts; `window` goes behind D."""
     args = tuple(map(int, dims))
-    rc, plan = _decode_plan("cln_%s_plan" % name, args)
+    rc, plan = _decode_plan("cln_%s_plan" % name, args + _paged_window(name, window))
     Hq, Hkv, max_pages, page, D = args[-5:]
     if rc == -2:
         if len(args) == 7 and D in (64, 128) and args[1] > 8:
@@ -777,14 +786,17 @@ def _paged_plan(name, *dims):
     return plan
 
 
-def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, out, lse, workspace):
+def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, out, lse, workspace,
+                     window=None):
     """The body of every attention entry over a paged cache. q, out: dtype [B,Hq,D] (q_dims = 3) or [B,T,Hq,D] (4), or with cu_q the packed
     [total_q,Hq,D]; the pools hold dtype, or with k_scale / v_scale e4m3; plan = the *_plan of a decode entry, which splits the keys and takes
-    a workspace, or None for a prefill entry: one launch, and what cannot be launched is told here, in the words of the plan."""
+    a workspace, or None for a prefill entry: one launch, and what cannot be launched is told here, in the words of the plan. window = the W of
+    a sliding-window entry: one more int behind D, for the entry and its plan."""
     packed, fp8 = cu_q is not None, k_scale is not None
+    win = _paged_window(name, window)
     fn = _lse_fns.get("cln_" + name) or _ext_fn(  # the prototype is put together on the first call only
         "cln_" + name, [ctypes.c_void_p] * (7 + packed + 2 * fp8) + ([ctypes.c_void_p, ctypes.c_longlong] if plan else [])
-        + [ctypes.c_int] * (q_dims + 4 + packed) + [ctypes.c_void_p])
+        + [ctypes.c_int] * (q_dims + 4 + packed + len(win)) + [ctypes.c_void_p])
     _decode_check((q, out) if fp8 else (q, k_pages, v_pages, out), (block_table, seqlens, cu_q) if packed else (block_table, seqlens), dtype)
     if q.dim() != q_dims or k_pages.dim() != 4 or block_table.dim() != 2:
         raise RuntimeError("Tensor size mismatch!")
@@ -806,7 +818,7 @@ def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table
         _check_dev(lse)
         _check_shape(lse, *lead)
     if plan:
-        ws, too_large = _decode_workspace(name, plan(*lead, Hkv, max_pages, page, D)[2], workspace, q.device), None
+        ws, too_large = _decode_workspace(name, plan(*lead, Hkv, max_pages, page, D, *win)[2], workspace, q.device), None
     else:
         Hq = lead[-1]
         if Hq % Hkv:
@@ -818,7 +830,7 @@ def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table
                      "%s: max_pages * page or B * Hkv * ceil(T * Hq / Hkv / 128) too large for one launch") % name
     more = (cu_q.data_ptr(),) if packed else (k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ()
     rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), *more, out.data_ptr(),
-            None if lse is None else lse.data_ptr(), *ws, *((B, *lead) if packed else lead), Hkv, P, max_pages, page, D, _stream())
+            None if lse is None else lse.data_ptr(), *ws, *((B, *lead) if packed else lead), Hkv, P, max_pages, page, D, *win, _stream())
     _raise(name, rc, too_large)
 
 
@@ -1010,6 +1022,33 @@ def fa2_decode_paged_multi_bf16(q, k_pages, v_pages, block_table, seqlens, out, 
     _paged_attention("fa2_decode_paged_multi_bf16", torch.bfloat16, 4, fa2_decode_paged_multi_bf16_plan, q, k_pages, v_pages, block_table, seqlens,
                      None, None,
                      None, out, lse, workspace)
+
+
+def fa2_prefill_paged_varlen_window_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, window, out, lse=None):
+    """fa2_prefill_paged_varlen_bf16 with a sliding window of `window` = W >= 1 keys: the query token at position p = len_b - T_b + t sees the
+    keys max(0, p - W + 1) … p (HF sliding_window = W, FlashAttention window_size = (W - 1, 0)); everything else as there, and with
+    W >= max_pages * page its bits. A tile walks about W + 128 / G + 128 keys whatever the length, and reads no table entry or pool row of a page
+    that ends at or before align_down(max(0, len_b - T_b - W + 1), max(page, 64)). C entry cln_fa2_prefill_paged_varlen_window_bf16
+    (include/cln_amd_ext.h); no CPU path."""
+    _paged_attention("fa2_prefill_paged_varlen_window_bf16", torch.bfloat16, 3, None, q, k_pages, v_pages, block_table, seqlens, cu_q, None, None,
+                     out, lse, None, window)
+
+
+def fa2_decode_paged_multi_window_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_window_bf16: the splits divide the span
+    min(max_pages * page, round_up(window + T - 1, U) + U), U = max(page, 128), not max_pages * page; a function of these eight numbers only, and
+    with window >= max_pages * page what fa2_decode_paged_multi_bf16_plan returns (cln_fa2_decode_paged_multi_window_bf16_plan,
+    include/cln_amd_ext.h). No GPU needed."""
+    return _paged_plan("fa2_decode_paged_multi_window_bf16", B, T, Hq, Hkv, max_pages, page, D, window=window)
+
+
+def fa2_decode_paged_multi_window_bf16(q, k_pages, v_pages, block_table, seqlens, window, out, lse=None, workspace=None):
+    """fa2_decode_paged_multi_bf16 with a sliding window of `window` = W >= 1 keys (the mask of fa2_prefill_paged_varlen_window_bf16); T in
+    1 … 8 and everything else as there, with fa2_decode_paged_multi_window_bf16_plan(...)[2] workspace bytes, and with W >= max_pages * page its
+    bits. Reads no table entry or pool row of a page that ends at or before align_down(max(0, len_b - T - W + 1), max(page, 128)). C entry
+    cln_fa2_decode_paged_multi_window_bf16 (include/cln_amd_ext.h); no CPU path."""
+    _paged_attention("fa2_decode_paged_multi_window_bf16", torch.bfloat16, 4, fa2_decode_paged_multi_window_bf16_plan, q, k_pages, v_pages,
+                     block_table, seqlens, None, None, None, out, lse, workspace, window)
 
 
 def fa2_decode_paged_fp8_plan(B, Hq, Hkv, max_pages, page, D):

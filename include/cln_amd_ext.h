@@ -279,6 +279,35 @@ int cln_fa2_decode_paged_multi_bf16(const void* q, const void* k_pages, const vo
                                     int max_pages, int page, int D, void* stream);
 int cln_fa2_decode_paged_multi_bf16_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, char* buf, int len);
 
+/* ---- SLIDING-WINDOW attention over the bf16 paged KV cache: cln_fa2_prefill_paged_varlen_bf16 and
+ * cln_fa2_decode_paged_multi_bf16[_plan|_describe] with one more argument, `int window` = W >= 1, behind D. The query token at absolute position
+ * p = len_b - T_b + t sees key j iff max(0, p - W + 1) <= j <= p: W keys, its own among them (HF sliding_window = W, FlashAttention
+ * window_size = (W - 1, 0)). Everything else is the unwindowed bf16 entry's: tensors, layouts, G, pages, D, alignment and aliasing rules, the
+ * clamping of seqlens and cu_q, untouched rows of no sequence, the numerics (fp32 scores scaled in fp32, P rounded once to bf16, fp32 m / l /
+ * accumulators, o rounded once at the store, natural-log lse), a row that sees no key -> o = 0, lse = -inf, no host read of device data,
+ * deterministic. With W >= max_pages page the results are bit for bit those of the unwindowed entries.
+ * Plan: cln_fa2_decode_paged_multi_window_bf16_plan divides not max_pages page but span = min(max_pages page, round_up(W + T - 1, U) + U) keys,
+ * U = max(page, 128), into `splits` chunks of `chunk` keys counted from base_b = align_down(max(0, len_b - T - W + 1), U) of each sequence; a
+ * function of its eight numbers only, and for W >= max_pages page the plan of cln_fa2_decode_paged_multi_bf16_plan. The workspace layout and size
+ * rule are unchanged.
+ * Stale table entries: with lo_min_b = max(0, len_b - T_b - W + 1), neither entry reads a block-table entry, or a pool row, of a logical page
+ * that ends at or before align_down(lo_min_b, U), U = max(page, 64) for the prefill and max(page, 128) for the decode: the caller may free or
+ * reuse those pages, and the table entries may be stale (any value).
+ * Returns the unwindowed entry's status for the same arguments, and -1 for window <= 0 (checked behind the shape).
+ */
+int cln_fa2_prefill_paged_varlen_window_bf16(const void* q, const void* k_pages, const void* v_pages, const int* block_table,
+                                             const int* seqlens, const int* cu_q, void* o, float* lse, int B, int total_q, int Hq, int Hkv, int P,
+                                             int max_pages, int page, int D, int window, void* stream);
+int cln_fa2_prefill_paged_varlen_window_bf16_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D, int window, char* buf,
+                                                      int len);
+int cln_fa2_decode_paged_multi_window_bf16_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window, int* splits,
+                                                int* chunk, long long* workspace_bytes);
+int cln_fa2_decode_paged_multi_window_bf16(const void* q, const void* k_pages, const void* v_pages, const int* block_table, const int* seqlens,
+                                           void* o, float* lse, void* workspace, long long workspace_bytes, int B, int T, int Hq, int Hkv, int P,
+                                           int max_pages, int page, int D, int window, void* stream);
+int cln_fa2_decode_paged_multi_window_bf16_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window, char* buf,
+                                                    int len);
+
 #ifdef __cplusplus
 }
 #endif
