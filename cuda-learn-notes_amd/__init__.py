@@ -234,6 +234,31 @@ def fa2_decode_paged_multi_window_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, w
     return host.fa2_decode_paged_multi_window_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window)
 
 
+def fa2_prefill_paged_varlen_window_sink_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, window, sinks, out, lse=None):
+    """fa2_prefill_paged_varlen_window_bf16 with attention sinks: sinks fp32 [Hq] on the GPU, one logit per query head in natural-log units (not
+    scaled by 1/sqrt(D)) that joins the softmax denominator of every row of its head and carries no value (HF GptOssAttention). lse is the log
+    of that denominator, the sink included; a row that sees no key stays O = 0, LSE = -inf. window = None: no window (full causal attention with
+    sinks). sinks of -inf give the bits of fa2_prefill_paged_varlen_window_bf16. C entry cln_fa2_prefill_paged_varlen_window_sink_bf16
+    (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_prefill_paged_varlen_window_sink_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, window, sinks, out, lse)
+
+
+def fa2_decode_paged_multi_window_sink_bf16(q, k_pages, v_pages, block_table, seqlens, window, sinks, out, lse=None, workspace=None):
+    """fa2_decode_paged_multi_window_bf16 with attention sinks (sinks fp32 [Hq], the semantics of fa2_prefill_paged_varlen_window_sink_bf16), T in
+    1 … 8; the sink enters once per row whatever the number of splits. window = None: no window. The plan and the workspace are those of
+    fa2_decode_paged_multi_window_bf16. C entry cln_fa2_decode_paged_multi_window_sink_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_decode_paged_multi_window_sink_bf16(q, k_pages, v_pages, block_table, seqlens, window, sinks, out, lse, workspace)
+
+
+def fa2_decode_paged_multi_window_sink_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_window_sink_bf16: what fa2_decode_paged_multi_window_bf16_plan returns;
+    window = None: no window. C entry cln_fa2_decode_paged_multi_window_sink_bf16_plan."""
+    from . import host
+    return host.fa2_decode_paged_multi_window_sink_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

@@ -1,5 +1,5 @@
-// The host side of the paged KV-cache entries (cln_kv_append_paged*, cln_fa2_prefill_paged*, cln_fa2_decode_paged*; DESIGN 4.4.6, 4.4.8, 4.4.9): one
-// definition of every argument check, shape check, plan and compile-time dispatch that the 15 compile units share. Host code only -- the kernels
+// The host side of the paged KV-cache entries (cln_kv_append_paged*, cln_fa2_prefill_paged*, cln_fa2_decode_paged*; DESIGN 4.4.6, 4.4.8 - 4.4.10): one
+// definition of every argument check, shape check, plan and compile-time dispatch that the 17 compile units share. Host code only -- the kernels
 // are siblings, one body per element type, for the measured reason given there; nothing here can change a kernel's schedule. A unit keeps its
 // entry points, its PagedKV / Args struct and its describe text.
 #pragma once
@@ -77,6 +77,7 @@ constexpr const char* kRot[] = {"rows copied bit for bit", "K and q rotated in h
 // ---------------------------------------------------------------- prefill
 // The pointers: n_in inputs, all required, 16-byte aligned up to the block table (index 3), 4-byte from there on; o 16-byte aligned; lse may be
 // null and is 4-byte aligned (not the 16 bytes of fa2d::check_pointers, which the decode entries use); no output is an input or the other output.
+// The *_sink_* entries put their fp32 sinks [Hq] last: required, 4-byte aligned, not an output.
 inline int prefill_args(const void* const* in, int n_in, const void* o, const float* lse, int P) {
   for (int i = 0; i < n_in; ++i)
     if (!in[i] || !cln_aligned(in[i], i >= 3 ? 4 : 16)) return CLN_ERR_BAD_ARG;
@@ -150,7 +151,7 @@ inline int multi_window_plan(int B, int T, int Hq, int Hkv, int max_pages, int p
 inline int multi_tiles(int T, const fa2d::PagedGeometry& g) { return (T * g.group + 15) / 16; }
 
 // The arguments of a decode entry in the order of their status codes: the pointers (fa2d::check_pointers), P, the status of the entry's plan
-// and, where the plan splits the keys, the workspace.
+// and, where the plan splits the keys, the workspace. The *_sink_* entries put their fp32 sinks [Hq] last in `in`, behind seqlens.
 inline int decode_args(const void* const* in, int n_in, const void* const (&out)[3], long long workspace_bytes, int P, int plan_rc,
                        const fa2d::Plan& p) {
   const int rc = fa2d::check_pointers(in, n_in, 3, out);

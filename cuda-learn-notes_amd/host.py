@@ -770,6 +770,16 @@ def _paged_window(name, window):
     return (int(window),)
 
 
+def _paged_sinks(sinks, q):
+    """What the *_sink_* entries ask of sinks before anything else is looked at: a contiguous torch.float32 [Hq], Hq = q's heads (its device is
+    checked with the other tensors')."""
+    _check_dtype(sinks, torch.float32)
+    if sinks.dim() != 1 or q.dim() < 2 or sinks.shape[0] != q.shape[-2]:
+        raise RuntimeError("Tensor size mismatch!")
+    if not sinks.is_contiguous():
+        raise RuntimeError("tensor must be contiguous (the kernels take raw data_ptr())")
+
+
 def _paged_plan(name, *dims, window=None):
     """The body of the paged *_plan wrappers: the C entry cln_<name>_plan for dims = (B, Hq, Hkv, max_pages, page, D), or with a T behind B
     for the multi-token entries, and its error texts; `window` goes behind D."""
@@ -787,17 +797,21 @@ def _paged_plan(name, *dims, window=None):
 
 
 def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, out, lse, workspace,
-                     window=None):
+                     window=None, sinks=None):
     """The body of every attention entry over a paged cache. q, out: dtype [B,Hq,D] (q_dims = 3) or [B,T,Hq,D] (4), or with cu_q the packed
     [total_q,Hq,D]; the pools hold dtype, or with k_scale / v_scale e4m3; plan = the *_plan of a decode entry, which splits the keys and takes
     a workspace, or None for a prefill entry: one launch, and what cannot be launched is told here, in the words of the plan. window = the W of
-    a sliding-window entry: one more int behind D, for the entry and its plan."""
-    packed, fp8 = cu_q is not None, k_scale is not None
+    a sliding-window entry: one more int behind D, for the entry and its plan. sinks = the fp32 [Hq] of a *_sink_* entry: the last input pointer."""
+    packed, fp8, sink = cu_q is not None, k_scale is not None, sinks is not None
     win = _paged_window(name, window)
+    if sink:
+        _paged_sinks(sinks, q)
     fn = _lse_fns.get("cln_" + name) or _ext_fn(  # the prototype is put together on the first call only
-        "cln_" + name, [ctypes.c_void_p] * (7 + packed + 2 * fp8) + ([ctypes.c_void_p, ctypes.c_longlong] if plan else [])
+        "cln_" + name, [ctypes.c_void_p] * (7 + packed + 2 * fp8 + sink) + ([ctypes.c_void_p, ctypes.c_longlong] if plan else [])
         + [ctypes.c_int] * (q_dims + 4 + packed + len(win)) + [ctypes.c_void_p])
     _decode_check((q, out) if fp8 else (q, k_pages, v_pages, out), (block_table, seqlens, cu_q) if packed else (block_table, seqlens), dtype)
+    if sink:
+        _check_dev(sinks)
     if q.dim() != q_dims or k_pages.dim() != 4 or block_table.dim() != 2:
         raise RuntimeError("Tensor size mismatch!")
     *lead, D = q.shape  # lead = [B, Hq], [B, T, Hq] or [total_q, Hq]
@@ -829,6 +843,8 @@ def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table
         too_large = ("%s: max_pages * page or Hkv * (total_q * Hq / Hkv / 128 + B) too large for one launch" if packed else
                      "%s: max_pages * page or B * Hkv * ceil(T * Hq / Hkv / 128) too large for one launch") % name
     more = (cu_q.data_ptr(),) if packed else (k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ()
+    if sink:
+        more += (sinks.data_ptr(),)
     rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), *more, out.data_ptr(),
             None if lse is None else lse.data_ptr(), *ws, *((B, *lead) if packed else lead), Hkv, P, max_pages, page, D, *win, _stream())
     _raise(name, rc, too_large)
@@ -1049,6 +1065,36 @@ def fa2_decode_paged_multi_window_bf16(q, k_pages, v_pages, block_table, seqlens
     cln_fa2_decode_paged_multi_window_bf16 (include/cln_amd_ext.h); no CPU path."""
     _paged_attention("fa2_decode_paged_multi_window_bf16", torch.bfloat16, 4, fa2_decode_paged_multi_window_bf16_plan, q, k_pages, v_pages,
                      block_table, seqlens, None, None, None, out, lse, workspace, window)
+
+
+_NO_WINDOW = 2 ** 31 - 1  # what window = None of the *_sink_* entries passes: a window past any cache
+
+
+def fa2_prefill_paged_varlen_window_sink_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, window, sinks, out, lse=None):
+    """fa2_prefill_paged_varlen_window_bf16 with attention sinks: sinks a contiguous torch.float32 [Hq] on q's device, one logit per query head in
+    natural-log units as the model stores it (sinks.float(); NOT scaled by 1/sqrt(D)), which joins the softmax denominator of every row of its
+    head and carries no value: O = sum_j exp(s_j) v_j / (sum_j exp(s_j) + exp(sinks[h])), lse = ln of that denominator, the sink included. A
+    row that sees no key stays O = 0, LSE = -inf. window = None: no window (2**31 - 1), the full-attention layers of gpt-oss. sinks of -inf
+    give the bits of fa2_prefill_paged_varlen_window_bf16; everything else as there. C entry cln_fa2_prefill_paged_varlen_window_sink_bf16
+    (include/cln_amd_ext.h); no CPU path."""
+    _paged_attention("fa2_prefill_paged_varlen_window_sink_bf16", torch.bfloat16, 3, None, q, k_pages, v_pages, block_table, seqlens, cu_q, None,
+                     None, out, lse, None, _NO_WINDOW if window is None else window, sinks)
+
+
+def fa2_decode_paged_multi_window_sink_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_window_sink_bf16: what fa2_decode_paged_multi_window_bf16_plan returns for the
+    same numbers -- the sink changes neither the splits nor the workspace; window = None: no window (2**31 - 1)
+    (cln_fa2_decode_paged_multi_window_sink_bf16_plan, include/cln_amd_ext.h). No GPU needed."""
+    return _paged_plan("fa2_decode_paged_multi_window_sink_bf16", B, T, Hq, Hkv, max_pages, page, D, window=_NO_WINDOW if window is None else window)
+
+
+def fa2_decode_paged_multi_window_sink_bf16(q, k_pages, v_pages, block_table, seqlens, window, sinks, out, lse=None, workspace=None):
+    """fa2_decode_paged_multi_window_bf16 with attention sinks (sinks, lse and the rows that see no key as for
+    fa2_prefill_paged_varlen_window_sink_bf16); T in 1 … 8, fa2_decode_paged_multi_window_sink_bf16_plan(...)[2] workspace bytes. The sink enters
+    once per row whatever the number of splits: at the final store with one split, in the combine with more. window = None: no window. C entry
+    cln_fa2_decode_paged_multi_window_sink_bf16 (include/cln_amd_ext.h); no CPU path."""
+    _paged_attention("fa2_decode_paged_multi_window_sink_bf16", torch.bfloat16, 4, fa2_decode_paged_multi_window_sink_bf16_plan, q, k_pages,
+                     v_pages, block_table, seqlens, None, None, None, out, lse, workspace, _NO_WINDOW if window is None else window, sinks)
 
 
 def fa2_decode_paged_fp8_plan(B, Hq, Hkv, max_pages, page, D):

@@ -308,6 +308,43 @@ int cln_fa2_decode_paged_multi_window_bf16(const void* q, const void* k_pages, c
 int cln_fa2_decode_paged_multi_window_bf16_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window, char* buf,
                                                     int len);
 
+/* ---- ATTENTION SINKS on the sliding-window bf16 paged entries: the *_window_bf16 entries above with one more input,
+ * `const float* sinks` = fp32 [Hq] on the device, the last input pointer: behind cu_q for the prefill, behind seqlens for the decode. sinks[h] is
+ * one logit per query head in natural-log units, as the model stores it (cast to fp32 by the caller) and NOT multiplied by 1/sqrt(D); it takes
+ * part in the softmax denominator of every row of head h and contributes no value (HF GptOssAttention: a sink column concatenated to the scaled
+ * logits, softmax, the column dropped).
+ * Mask: position, causal edge, window, ragged and right-aligned batches, len_b < T_b, the clamping of seqlens and cu_q, stale table entries and
+ * the rows of no sequence are exactly those of the *_window_bf16 entries. A window past the cache (any W >= max_pages page, e.g. 2^31 - 1) is
+ * full causal attention with sinks.
+ * A row that sees at least one key, with s_j = q.k_j / sqrt(D) over its visible keys j:
+ *   o   = sum_j exp(s_j) v_j / (sum_j exp(s_j) + exp(sinks[h]))
+ *   lse = ln(sum_j exp(s_j) + exp(sinks[h])): the log of the denominator ACTUALLY USED, the sink included -- not the log-sum-exp over the keys.
+ * Evaluated without overflow for every sink whose sink log2(e) is finite in fp32: with m, l the row's fp32 maximum and sum in log2 units,
+ * m' = max(m, sink2), o and l are scaled by exp2(m - m') and exp2(sink2 - m') is added to l; sink2 = sinks[h] log2(e) is formed once, in fp32.
+ * A row that sees no key (a right-aligned padding row, len_b = 0, len_b < T_b): o = 0, lse = -inf, as in the *_window_bf16 entries; the sink
+ * does not turn a non-row into a row.
+ * The sink enters once per row whatever the number of splits: at the final normalisation of the prefill kernel and of the decode's stream kernel
+ * when splits == 1, in the combine kernel when splits > 1 (the splits store raw partials; the workspace layout is unchanged).
+ * sinks[h] = -inf, or a finite sink so far below the row's maximum that exp2 gives 0: o and lse are bit for bit those of the *_window_bf16 entry.
+ * Plan: cln_fa2_decode_paged_multi_window_sink_bf16_plan is cln_fa2_decode_paged_multi_window_bf16_plan; the sink changes neither the splits nor
+ * the workspace.
+ * sinks is required (without sinks use the *_window_bf16 entry), 4-byte aligned and no output. Returns the *_window_bf16 entry's status for the
+ * same arguments in the same order; a null or misaligned sinks, or sinks equal to o, lse or workspace, is -1 where a bad seqlens is.
+ */
+int cln_fa2_prefill_paged_varlen_window_sink_bf16(const void* q, const void* k_pages, const void* v_pages, const int* block_table,
+                                                  const int* seqlens, const int* cu_q, const float* sinks, void* o, float* lse, int B, int total_q,
+                                                  int Hq, int Hkv, int P, int max_pages, int page, int D, int window, void* stream);
+int cln_fa2_prefill_paged_varlen_window_sink_bf16_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D, int window,
+                                                           char* buf, int len);
+int cln_fa2_decode_paged_multi_window_sink_bf16_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window, int* splits,
+                                                     int* chunk, long long* workspace_bytes);
+int cln_fa2_decode_paged_multi_window_sink_bf16(const void* q, const void* k_pages, const void* v_pages, const int* block_table,
+                                                const int* seqlens, const float* sinks, void* o, float* lse, void* workspace,
+                                                long long workspace_bytes, int B, int T, int Hq, int Hkv, int P, int max_pages, int page, int D,
+                                                int window, void* stream);
+int cln_fa2_decode_paged_multi_window_sink_bf16_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window, char* buf,
+                                                         int len);
+
 #ifdef __cplusplus
 }
 #endif
