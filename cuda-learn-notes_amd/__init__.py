@@ -259,6 +259,43 @@ def fa2_decode_paged_multi_window_sink_bf16_plan(B, T, Hq, Hkv, max_pages, page,
     return host.fa2_decode_paged_multi_window_sink_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window)
 
 
+def kv_append_paged_varlen_bf16_fp8(k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, q=None, q_out=None,
+                                    rope_table=None, rope="none"):
+    """kv_append_paged_varlen_bf16 into a paged KV cache held in FP8: bf16 rows, torch.float8_e4m3fn pools [P,Hkv,page,D], k_scale / v_scale fp32
+    [Hkv] (a stored byte c of KV head h means e4m3(c) * scale[h]); every element is e4m3(clamp(y / scale, +-448)) of the bf16 input or the fp32
+    rotation result; q is rotated and written as bf16. C entry cln_kv_append_paged_varlen_bf16_fp8 (include/cln_amd_ext.h). Not a reference
+    name."""
+    from . import host
+    return host.kv_append_paged_varlen_bf16_fp8(k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, q, q_out, rope_table,
+                                                rope)
+
+
+def fa2_prefill_paged_varlen_window_sink_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, window, sinks, out, lse=None):
+    """fa2_prefill_paged_varlen_window_sink_bf16 over a paged KV cache held in FP8 (torch.float8_e4m3fn pools, k_scale / v_scale fp32 [Hkv]): the
+    bf16 entry's function on the dequantised pools. window = None: no window; sinks = None: no sink. C entry
+    cln_fa2_prefill_paged_varlen_window_sink_bf16_fp8 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_prefill_paged_varlen_window_sink_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, window, sinks, out,
+                                                              lse)
+
+
+def fa2_decode_paged_multi_window_sink_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, window, sinks, out, lse=None,
+                                                workspace=None):
+    """fa2_decode_paged_multi_window_sink_bf16 over a paged KV cache held in FP8 (torch.float8_e4m3fn pools, k_scale / v_scale fp32 [Hkv]), T in
+    1 … 8. window = None: no window; sinks = None: no sink. The plan and the workspace are those of fa2_decode_paged_multi_window_bf16. C entry
+    cln_fa2_decode_paged_multi_window_sink_bf16_fp8 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_decode_paged_multi_window_sink_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, window, sinks, out, lse,
+                                                            workspace)
+
+
+def fa2_decode_paged_multi_window_sink_bf16_fp8_plan(B, T, Hq, Hkv, max_pages, page, D, window):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_window_sink_bf16_fp8: what fa2_decode_paged_multi_window_bf16_plan returns;
+    window = None: no window. C entry cln_fa2_decode_paged_multi_window_sink_bf16_fp8_plan."""
+    from . import host
+    return host.fa2_decode_paged_multi_window_sink_bf16_fp8_plan(B, T, Hq, Hkv, max_pages, page, D, window)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

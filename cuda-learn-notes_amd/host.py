@@ -797,17 +797,19 @@ def _paged_plan(name, *dims, window=None):
 
 
 def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, out, lse, workspace,
-                     window=None, sinks=None):
+                     window=None, sinks=None, sinks_optional=False):
     """The body of every attention entry over a paged cache. q, out: dtype [B,Hq,D] (q_dims = 3) or [B,T,Hq,D] (4), or with cu_q the packed
     [total_q,Hq,D]; the pools hold dtype, or with k_scale / v_scale e4m3; plan = the *_plan of a decode entry, which splits the keys and takes
     a workspace, or None for a prefill entry: one launch, and what cannot be launched is told here, in the words of the plan. window = the W of
-    a sliding-window entry: one more int behind D, for the entry and its plan. sinks = the fp32 [Hq] of a *_sink_* entry: the last input pointer."""
+    a sliding-window entry: one more int behind D, for the entry and its plan. sinks = the fp32 [Hq] of a *_sink_* entry: the last input pointer;
+    sinks_optional: the entry has that pointer and takes NULL for sinks = None."""
     packed, fp8, sink = cu_q is not None, k_scale is not None, sinks is not None
+    sink_ptr = sink or sinks_optional
     win = _paged_window(name, window)
     if sink:
         _paged_sinks(sinks, q)
     fn = _lse_fns.get("cln_" + name) or _ext_fn(  # the prototype is put together on the first call only
-        "cln_" + name, [ctypes.c_void_p] * (7 + packed + 2 * fp8 + sink) + ([ctypes.c_void_p, ctypes.c_longlong] if plan else [])
+        "cln_" + name, [ctypes.c_void_p] * (7 + packed + 2 * fp8 + sink_ptr) + ([ctypes.c_void_p, ctypes.c_longlong] if plan else [])
         + [ctypes.c_int] * (q_dims + 4 + packed + len(win)) + [ctypes.c_void_p])
     _decode_check((q, out) if fp8 else (q, k_pages, v_pages, out), (block_table, seqlens, cu_q) if packed else (block_table, seqlens), dtype)
     if sink:
@@ -842,9 +844,9 @@ def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table
         ws = ()
         too_large = ("%s: max_pages * page or Hkv * (total_q * Hq / Hkv / 128 + B) too large for one launch" if packed else
                      "%s: max_pages * page or B * Hkv * ceil(T * Hq / Hkv / 128) too large for one launch") % name
-    more = (cu_q.data_ptr(),) if packed else (k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ()
-    if sink:
-        more += (sinks.data_ptr(),)
+    more = ((cu_q.data_ptr(),) if packed else ()) + ((k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ())
+    if sink_ptr:
+        more += (sinks.data_ptr() if sink else None,)
     rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), *more, out.data_ptr(),
             None if lse is None else lse.data_ptr(), *ws, *((B, *lead) if packed else lead), Hkv, P, max_pages, page, D, *win, _stream())
     _raise(name, rc, too_large)
@@ -903,7 +905,7 @@ def _kv_append_paged(name, dtype, k_new, v_new, k_pages, v_pages, block_table, s
     if Hq % Hkv:
         raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
     ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    more = (cu_q.data_ptr(),) if packed else (k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ()
+    more = ((cu_q.data_ptr(),) if packed else ()) + ((k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ())
     rc = fn(k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), *more, ptr(q),
             ptr(q_out), ptr(rope_table), *((B, *lead) if packed else lead), Hq, Hkv, P, max_pages, page, D, max_pos, mode, _stream())
     _raise(name, rc, ("%s: max_pages * page or total_q too large for one launch" if packed else
@@ -1153,3 +1155,45 @@ def kv_append_paged_fp8(k_new, v_new, k_pages, v_pages, block_table, seqlens, k_
     _kv_append_paged("kv_append_paged_fp8", torch.float16, k_new, v_new, k_pages, v_pages, block_table, seqlens, None, k_scale, v_scale, q, q_out,
                      rope_table,
                      rope)
+
+
+def kv_append_paged_varlen_bf16_fp8(k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, q=None, q_out=None,
+                                    rope_table=None, rope="none"):
+    """kv_append_paged_varlen_bf16 into a cache held in FP8; one launch. k_new, v_new torch.bfloat16 [total_q,Hkv,D]; k_pages, v_pages
+    torch.float8_e4m3fn [P,Hkv,page,D], written in place; k_scale, v_scale fp32 [Hkv] on the GPU. The packed rows, cu_q, positions, liveness,
+    rope, q, q_out and rope_table are those of kv_append_paged_varlen_bf16; q is rotated and written as bf16 without a scale. Every element of a
+    live K or V row is stored as e4m3(clamp(y * (1 / scale[h]), -448, 448)), fp32 arithmetic, round to nearest even, y the bf16 input or the fp32
+    rotation result (not rounded to bf16 in between). The scales must be finite and > 0 and the inputs finite (the caller's contract, not
+    checked). Deterministic. C entry cln_kv_append_paged_varlen_bf16_fp8 (include/cln_amd_ext.h); no CPU path."""
+    _kv_append_paged("kv_append_paged_varlen_bf16_fp8", torch.bfloat16, k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale,
+                     q, q_out, rope_table, rope)
+
+
+def fa2_prefill_paged_varlen_window_sink_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, window, sinks, out, lse=None):
+    """fa2_prefill_paged_varlen_window_sink_bf16 over a paged KV cache held in FP8: q, out torch.bfloat16 [total_q,Hq,D]; k_pages, v_pages
+    torch.float8_e4m3fn [P,Hkv,page,D]; k_scale, v_scale fp32 [Hkv] on the GPU. A stored byte c of KV head h means e4m3(c) * scale[h]; the scales
+    must be finite and > 0 and the live bytes no NaN code (the caller's contract, not checked). The function is that of the bf16 entry on the
+    dequantised pools: the codes become bf16 exactly, k_scale multiplies the fp32 score multiplier and v_scale the normalisation; nothing passes
+    through fp16. window = None: no window (2**31 - 1). sinks = None: no sink, the bits of sinks that are all -inf. Everything else as there. C
+    entry cln_fa2_prefill_paged_varlen_window_sink_bf16_fp8 (include/cln_amd_ext.h); no CPU path."""
+    _paged_attention("fa2_prefill_paged_varlen_window_sink_bf16_fp8", torch.bfloat16, 3, None, q, k_pages, v_pages, block_table, seqlens, cu_q,
+                     k_scale, v_scale, out, lse, None, _NO_WINDOW if window is None else window, sinks, True)
+
+
+def fa2_decode_paged_multi_window_sink_bf16_fp8_plan(B, T, Hq, Hkv, max_pages, page, D, window):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_window_sink_bf16_fp8: what fa2_decode_paged_multi_window_bf16_plan returns for
+    the same numbers -- neither the FP8 pools nor the sink change the splits or the fp32 workspace; window = None: no window (2**31 - 1)
+    (cln_fa2_decode_paged_multi_window_sink_bf16_fp8_plan, include/cln_amd_ext.h). No GPU needed."""
+    return _paged_plan("fa2_decode_paged_multi_window_sink_bf16_fp8", B, T, Hq, Hkv, max_pages, page, D,
+                       window=_NO_WINDOW if window is None else window)
+
+
+def fa2_decode_paged_multi_window_sink_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, window, sinks, out, lse=None,
+                                                workspace=None):
+    """fa2_decode_paged_multi_window_sink_bf16 over a paged KV cache held in FP8 (pools, scales, numerics, window = None and sinks = None as for
+    fa2_prefill_paged_varlen_window_sink_bf16_fp8; v_scale multiplies each split's fp32 partial); q, out torch.bfloat16 [B,T,Hq,D], T in 1 … 8,
+    fa2_decode_paged_multi_window_sink_bf16_fp8_plan(...)[2] workspace bytes. C entry cln_fa2_decode_paged_multi_window_sink_bf16_fp8
+    (include/cln_amd_ext.h); no CPU path."""
+    _paged_attention("fa2_decode_paged_multi_window_sink_bf16_fp8", torch.bfloat16, 4, fa2_decode_paged_multi_window_sink_bf16_fp8_plan, q, k_pages,
+                     v_pages, block_table, seqlens, None, k_scale, v_scale, out, lse, workspace, _NO_WINDOW if window is None else window, sinks,
+                     True)

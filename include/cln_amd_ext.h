@@ -345,6 +345,56 @@ int cln_fa2_decode_paged_multi_window_sink_bf16(const void* q, const void* k_pag
 int cln_fa2_decode_paged_multi_window_sink_bf16_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window, char* buf,
                                                          int len);
 
+/* ---- FP8 (OCP e4m3fn) KV POOLS on the bf16 paged path, with window and sinks: a bf16 model keeps its cache in one
+ * byte per element. Three entries, the most general form -- a full-attention layer passes a window past the cache, a layer without sinks passes
+ * sinks = NULL. k_pages / v_pages are e4m3fn [P,Hkv,page,D]; k_scale / v_scale are fp32 [Hkv] on the device, finite and > 0, with the meaning and
+ * the rules of the fp16 FP8 entries (section 14): a stored byte c of KV head h means e4m3(c) * scale[h], and the live bytes are no NaN code
+ * (0x7f, 0xff). q, o, k_new, v_new and q_out are bf16. The scales stand behind cu_q (append, prefill) or seqlens (decode), 4-byte aligned.
+ *
+ * cln_kv_append_paged_varlen_bf16_fp8: cln_kv_append_paged_varlen_bf16 with the quantising store of cln_kv_append_paged_fp8 -- the packed cu_q
+ * prologue, liveness, clamping, the rows of no sequence left untouched, q -> q_out rotated and stored as bf16 (q_out == q allowed). Per element of
+ * a live K or V row the byte is e4m3(clamp(y * (1.0f / scale[h]), -448, 448)), IEEE fp32, round to nearest even, y the bf16 input or the fp32
+ * rotation result with no bf16 rounding in between. Status: that of cln_kv_append_paged_varlen_bf16 for the same arguments; a null or misaligned
+ * scale, or a scale that is an output, is -1 where a bad cu_q is.
+ *
+ * cln_fa2_prefill_paged_varlen_window_sink_bf16_fp8 / cln_fa2_decode_paged_multi_window_sink_bf16_fp8: the function of the *_window_sink_bf16
+ * entries above evaluated on the dequantised pools -- position, causal edge, window max(0, p - W + 1) <= j <= p, ragged and right-aligned
+ * batches, len_b < T_b, stale table entries (the same U), rows that see no key (o = 0, lse = -inf) and lse = the log of the denominator used are
+ * theirs. Any window >= max_pages page means no window. sinks may be NULL: no sink, bit for bit the result of a [Hq] tensor of -inf.
+ * Numerics: every code is converted once to bf16, exactly (v_cvt_scalef32_pk_bf16_fp8 at scale 2^0; every e4m3 value is a bf16 value); both
+ * products run on v_mfma_f32_16x16x32_bf16 on the unscaled codes; k_scale[kvh] log2(e) / sqrt(D) is the fp32 score multiplier, one product per
+ * workgroup; v_scale[kvh] multiplies the prefill's normalisation, respectively the decode's fp32 partial in front of its store. P is rounded
+ * once to bf16 (round to nearest even); m, l, accumulators, partials and the combine are fp32; o is rounded once to bf16 at the store. Nothing
+ * passes through fp16.
+ * Plan: cln_fa2_decode_paged_multi_window_sink_bf16_fp8_plan is cln_fa2_decode_paged_multi_window_bf16_plan, status included; the workspace is
+ * fp32 and has the same layout, and the splits are merged by the *_window_sink_bf16 entry's combine kernel (without sinks: the *_window_bf16
+ * entry's).
+ * Status: that of the *_window_sink_bf16 entry for the same arguments in the same order, except that sinks == NULL is legal (a misaligned sinks,
+ * or sinks equal to an output, stays -1); a null or misaligned scale, or a scale equal to an output, is -1 where a bad seqlens is; window <= 0 is
+ * -1, checked behind the shape. D in {64, 128}, Hq / Hkv in {1, 2, 4, 8}, page in {16, 32, 64, 128, 256}, T <= 8 for the decode.
+ */
+int cln_kv_append_paged_varlen_bf16_fp8(const void* k_new, const void* v_new, void* k_pages, void* v_pages, const int* block_table,
+                                        const int* seqlens, const int* cu_q, const float* k_scale, const float* v_scale, const void* q,
+                                        void* q_out, const float* rope_table, int B, int total_q, int Hq, int Hkv, int P, int max_pages, int page,
+                                        int D, int max_pos, int rope_mode, void* stream);
+int cln_kv_append_paged_varlen_bf16_fp8_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D, int rope_mode, char* buf,
+                                                 int len);
+int cln_fa2_prefill_paged_varlen_window_sink_bf16_fp8(const void* q, const void* k_pages, const void* v_pages, const int* block_table,
+                                                      const int* seqlens, const int* cu_q, const float* k_scale, const float* v_scale,
+                                                      const float* sinks /* may be NULL */, void* o, float* lse, int B, int total_q, int Hq,
+                                                      int Hkv, int P, int max_pages, int page, int D, int window, void* stream);
+int cln_fa2_prefill_paged_varlen_window_sink_bf16_fp8_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D, int window,
+                                                               char* buf, int len);
+int cln_fa2_decode_paged_multi_window_sink_bf16_fp8_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window, int* splits,
+                                                         int* chunk, long long* workspace_bytes);
+int cln_fa2_decode_paged_multi_window_sink_bf16_fp8(const void* q, const void* k_pages, const void* v_pages, const int* block_table,
+                                                    const int* seqlens, const float* k_scale, const float* v_scale,
+                                                    const float* sinks /* may be NULL */, void* o, float* lse, void* workspace,
+                                                    long long workspace_bytes, int B, int T, int Hq, int Hkv, int P, int max_pages, int page,
+                                                    int D, int window, void* stream);
+int cln_fa2_decode_paged_multi_window_sink_bf16_fp8_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window, char* buf,
+                                                             int len);
+
 #ifdef __cplusplus
 }
 #endif
