@@ -296,6 +296,54 @@ def fa2_decode_paged_multi_window_sink_bf16_fp8_plan(B, T, Hq, Hkv, max_pages, p
     return host.fa2_decode_paged_multi_window_sink_bf16_fp8_plan(B, T, Hq, Hkv, max_pages, page, D, window)
 
 
+def fa2_prefill_paged_varlen_window_sink_anyg_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, window, sinks, out, lse=None):
+    """fa2_prefill_paged_varlen_window_sink_bf16 for any group size Hq / Hkv in 1 … 16 (Qwen2.5's 7, 5 and 6, Llama-3.2-3B's 3, 12, 16), not a
+    power of two only; window = None: no window, sinks = None: no sink. For Hq / Hkv in {1, 2, 4, 8} the sibling's bits. C entry
+    cln_fa2_prefill_paged_varlen_window_sink_anyg_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_prefill_paged_varlen_window_sink_anyg_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, window, sinks, out, lse)
+
+
+def fa2_decode_paged_multi_window_sink_anyg_bf16(q, k_pages, v_pages, block_table, seqlens, window, sinks, out, lse=None, workspace=None):
+    """fa2_decode_paged_multi_window_sink_bf16 for any group size Hq / Hkv in 1 … 16, T in 1 … 8 with T * Hq / Hkv <= 64; window = None: no
+    window, sinks = None: no sink. C entry cln_fa2_decode_paged_multi_window_sink_anyg_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_decode_paged_multi_window_sink_anyg_bf16(q, k_pages, v_pages, block_table, seqlens, window, sinks, out, lse, workspace)
+
+
+def fa2_decode_paged_multi_window_sink_anyg_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_window_sink_anyg_bf16: for Hq / Hkv in {1, 2, 4, 8} what
+    fa2_decode_paged_multi_window_sink_bf16_plan returns; window = None: no window. C entry cln_fa2_decode_paged_multi_window_sink_anyg_bf16_plan."""
+    from . import host
+    return host.fa2_decode_paged_multi_window_sink_anyg_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window)
+
+
+def fa2_prefill_paged_varlen_window_sink_anyg_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, window, sinks, out,
+                                                       lse=None):
+    """fa2_prefill_paged_varlen_window_sink_bf16_fp8 for any group size Hq / Hkv in 1 … 16; window = None: no window, sinks = None: no sink. C
+    entry cln_fa2_prefill_paged_varlen_window_sink_anyg_bf16_fp8 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_prefill_paged_varlen_window_sink_anyg_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, window, sinks,
+                                                                   out, lse)
+
+
+def fa2_decode_paged_multi_window_sink_anyg_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, window, sinks, out, lse=None,
+                                                     workspace=None):
+    """fa2_decode_paged_multi_window_sink_bf16_fp8 for any group size Hq / Hkv in 1 … 16, T in 1 … 8 with T * Hq / Hkv <= 64; window = None: no
+    window, sinks = None: no sink. C entry cln_fa2_decode_paged_multi_window_sink_anyg_bf16_fp8 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_decode_paged_multi_window_sink_anyg_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, window, sinks, out,
+                                                                 lse, workspace)
+
+
+def fa2_decode_paged_multi_window_sink_anyg_bf16_fp8_plan(B, T, Hq, Hkv, max_pages, page, D, window):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_window_sink_anyg_bf16_fp8: what
+    fa2_decode_paged_multi_window_sink_anyg_bf16_plan returns; window = None: no window. C entry
+    cln_fa2_decode_paged_multi_window_sink_anyg_bf16_fp8_plan."""
+    from . import host
+    return host.fa2_decode_paged_multi_window_sink_anyg_bf16_fp8_plan(B, T, Hq, Hkv, max_pages, page, D, window)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

@@ -1,5 +1,5 @@
 // The host side of the paged KV-cache entries (cln_kv_append_paged*, cln_fa2_prefill_paged*, cln_fa2_decode_paged*): one
-// definition of every argument check, shape check, plan and compile-time dispatch that the 17 compile units share. Host code only -- the kernels
+// definition of every argument check, shape check, plan and compile-time dispatch that the 21 compile units share. Host code only -- the kernels
 // are siblings, one body per element type, for the measured reason given there; nothing here can change a kernel's schedule. A unit keeps its
 // entry points, its PagedKV / Args struct and its describe text.
 #pragma once
@@ -149,6 +149,50 @@ inline int multi_window_plan(int B, int T, int Hq, int Hkv, int max_pages, int p
 }
 // the 16-row MFMA tiles of the T G query rows of a KV head: 1 ... 4, as T <= 8 and G <= 8
 inline int multi_tiles(int T, const fa2d::PagedGeometry& g) { return (T * g.group + 15) / 16; }
+
+// ---------------------------------------------------------------- any group size (the *_anyg_* entries)
+// fa2d::paged_geometry for a group size G = Hq / Hkv that is any integer 1 ... kMaxGroupAnyG, not a power of two only: -1 for a non-positive
+// dimension or Hq % Hkv != 0, -2 for a larger G, another page or max_pages page >= 2^31. g_shift stays 0 and means nothing: these kernels take
+// g->group and divide.
+constexpr int kMaxGroupAnyG = 16;
+inline int geometry_anyg(int Hq, int Hkv, int max_pages, int page, fa2d::PagedGeometry* g) {
+  if (Hq <= 0 || Hkv <= 0 || max_pages <= 0 || page <= 0 || Hq % Hkv != 0) return CLN_ERR_BAD_ARG;
+  if (Hq / Hkv > kMaxGroupAnyG) return CLN_ERR_UNSUPPORTED;
+  const int rc = fa2d::paged_geometry(1, 1, max_pages, page, g);  // the page size and max_pages page
+  g->group = Hq / Hkv;
+  return rc;
+}
+// prefill_varlen_shape on it: slots = total_q G / 128 + B
+inline int prefill_varlen_shape_anyg(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D, fa2d::PagedGeometry* g,
+                                     long long* slots) {
+  if (B <= 0 || total_q <= 0 || D <= 0) return CLN_ERR_BAD_ARG;
+  const int rc = geometry_anyg(Hq, Hkv, max_pages, page, g);
+  if (rc != CLN_OK) return rc;
+  if (D != 64 && D != 128) return CLN_ERR_UNSUPPORTED;
+  const long long R = (long long)total_q * g->group;
+  *slots = R / fa2pp::kRowTile + B;
+  if (R > 0x7fffffffLL || *slots > 0xffffffffLL / fa2d::kThreads / Hkv) return CLN_ERR_UNSUPPORTED;
+  return CLN_OK;
+}
+// The tokens a prefill tile of 128 rows covers at most, for a describe text: a tile starts at row 128 i of its sequence, inside token 128 i / G at
+// offset o = 128 i mod G, and its rows o ... o + 127 touch floor((o + 127) / G) + 1 tokens. o is a multiple of d = gcd(G, 128) = the lowest set
+// bit of G (G <= 16) and reaches G - d. Where G divides 128, o = 0: 128 / G, the siblings' number; at G = 7 it is 20, where 128 / G is 18.
+inline int prefill_tile_tokens_anyg(int G) { return (G - (G & -G) + fa2pp::kRowTile - 1) / G + 1; }
+static_assert(fa2pp::kRowTile == 128, "the lowest set bit of G <= 16 is gcd(G, kRowTile)");
+// multi_window_plan on it: the same fa2d::split_plan of the same numbers, so for G in {1, 2, 4, 8} the sibling's plan. The T G rows of a
+// (sequence, KV head) are at most 4 row tiles of 16: T <= 8 and T G <= 64, else -2.
+constexpr int kMaxRowsAnyG = 64;
+inline int multi_window_plan_anyg(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window, fa2d::PagedGeometry* g,
+                                  fa2d::Plan* p) {
+  if (B <= 0 || T <= 0 || D <= 0) return CLN_ERR_BAD_ARG;
+  int rc = geometry_anyg(Hq, Hkv, max_pages, page, g);
+  if (rc != CLN_OK) return rc;
+  if ((D != 64 && D != 128) || T > fa2pm::kMaxT || T * g->group > kMaxRowsAnyG) return CLN_ERR_UNSUPPORTED;
+  rc = window_arg(window);
+  if (rc != CLN_OK) return rc;
+  return fa2d::split_plan((long long)B * Hkv, (long long)B * T * Hq, multi_window_span(T, page, window, g->Nmax), multi_window_unit(page), D, p);
+}
+// multi_tiles serves it as it is: ceil(T G / 16), 1 ... 4
 
 // The arguments of a decode entry in the order of their status codes: the pointers (fa2d::check_pointers), P, the status of the entry's plan
 // and, where the plan splits the keys, the workspace. The *_sink_* entries put their fp32 sinks [Hq] last in `in`, behind seqlens.

@@ -736,15 +736,22 @@ def fa2_decode(q, k_cache, v_cache, seqlens, out, lse=None, workspace=None):
 
 
 _PAGED_GROUPS, _PAGED_PAGES = (1, 2, 4, 8), (16, 32, 64, 128, 256)
+_PAGED_GROUPS_ANYG, _PAGED_ROWS_ANYG = tuple(range(1, 17)), 64  # the *_anyg_* entries: any G = Hq / Hkv in 1 … 16; the decode: T * G <= 64
 _ROPE_MODES = {"none": 0, "half": 1, "interleaved": 2}
+
+
+def _paged_groups(name):
+    """The group sizes Hq / Hkv the paged attention entry `name` takes."""
+    return _PAGED_GROUPS_ANYG if "_anyg_" in name else _PAGED_GROUPS
 
 
 def _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D):
     """The RuntimeError for status -2 of the paged decode entry `name`."""
     if D not in (64, 128):
         return RuntimeError("%s: headdim %d not supported (64 or 128)" % (name, D))
-    if Hkv > 0 and Hq % Hkv == 0 and Hq // Hkv not in _PAGED_GROUPS:
-        return RuntimeError("%s: group size %d (= Hq %d / Hkv %d) not supported (1, 2, 4 or 8)" % (name, Hq // Hkv, Hq, Hkv))
+    if Hkv > 0 and Hq % Hkv == 0 and Hq // Hkv not in _paged_groups(name):
+        return RuntimeError("%s: group size %d (= Hq %d / Hkv %d) not supported (%s)"
+                            % (name, Hq // Hkv, Hq, Hkv, "1 … 16" if "_anyg_" in name else "1, 2, 4 or 8"))
     if page not in _PAGED_PAGES:
         return RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
     return RuntimeError("%s: max_pages * page or B * Hkv * splits too large for one launch" % name)
@@ -789,6 +796,10 @@ def _paged_plan(name, *dims, window=None):
     if rc == -2:
         if len(args) == 7 and D in (64, 128) and args[1] > 8:
             raise RuntimeError("%s: T %d not supported (1 … 8)" % (name, args[1]))
+        if (len(args) == 7 and D in (64, 128) and "_anyg_" in name and Hkv > 0 and Hq % Hkv == 0 and Hq // Hkv in _PAGED_GROUPS_ANYG
+                and args[1] * (Hq // Hkv) > _PAGED_ROWS_ANYG):
+            raise RuntimeError("%s: T %d x group size %d = %d query rows per KV head not supported (at most %d)"
+                               % (name, args[1], Hq // Hkv, args[1] * (Hq // Hkv), _PAGED_ROWS_ANYG))
         raise _paged_unsupported(name, args[0], Hq, Hkv, max_pages, page, D)
     if rc == -1 and Hkv > 0 and Hq % Hkv:
         raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
@@ -839,7 +850,7 @@ def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table
         Hq = lead[-1]
         if Hq % Hkv:
             raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
-        if D not in (64, 128) or Hq // Hkv not in _PAGED_GROUPS or page not in _PAGED_PAGES:
+        if D not in (64, 128) or Hq // Hkv not in _paged_groups(name) or page not in _PAGED_PAGES:
             raise _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D)
         ws = ()
         too_large = ("%s: max_pages * page or Hkv * (total_q * Hq / Hkv / 128 + B) too large for one launch" if packed else
@@ -1197,3 +1208,58 @@ def fa2_decode_paged_multi_window_sink_bf16_fp8(q, k_pages, v_pages, block_table
     _paged_attention("fa2_decode_paged_multi_window_sink_bf16_fp8", torch.bfloat16, 4, fa2_decode_paged_multi_window_sink_bf16_fp8_plan, q, k_pages,
                      v_pages, block_table, seqlens, None, k_scale, v_scale, out, lse, workspace, _NO_WINDOW if window is None else window, sinks,
                      True)
+
+
+def fa2_prefill_paged_varlen_window_sink_anyg_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, window, sinks, out, lse=None):
+    """fa2_prefill_paged_varlen_window_sink_bf16 for any group size Hq / Hkv in 1 … 16 (3, 5, 6, 7, 12, 16 …), not a power of two only: tensors,
+    lengths, window, sinks, lse and errors as there, and for Hq / Hkv in {1, 2, 4, 8} its bits. window = None: no window (2**31 - 1). sinks =
+    None: no sink, the bits of sinks that are all -inf. C entry cln_fa2_prefill_paged_varlen_window_sink_anyg_bf16 (include/cln_amd_ext.h); no
+    CPU path."""
+    _paged_attention("fa2_prefill_paged_varlen_window_sink_anyg_bf16", torch.bfloat16, 3, None, q, k_pages, v_pages, block_table, seqlens, cu_q,
+                     None, None, out, lse, None, _NO_WINDOW if window is None else window, sinks, True)
+
+
+def fa2_decode_paged_multi_window_sink_anyg_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_window_sink_anyg_bf16: for Hq / Hkv in {1, 2, 4, 8} what
+    fa2_decode_paged_multi_window_sink_bf16_plan returns, and the same function of (B * Hkv, B * T * Hq, span, unit, D) for every other Hq / Hkv
+    in 1 … 16; T in 1 … 8 with T * Hq / Hkv <= 64; window = None: no window (2**31 - 1)
+    (cln_fa2_decode_paged_multi_window_sink_anyg_bf16_plan, include/cln_amd_ext.h). No GPU needed."""
+    return _paged_plan("fa2_decode_paged_multi_window_sink_anyg_bf16", B, T, Hq, Hkv, max_pages, page, D,
+                       window=_NO_WINDOW if window is None else window)
+
+
+def fa2_decode_paged_multi_window_sink_anyg_bf16(q, k_pages, v_pages, block_table, seqlens, window, sinks, out, lse=None, workspace=None):
+    """fa2_decode_paged_multi_window_sink_bf16 for any group size Hq / Hkv in 1 … 16: q, out torch.bfloat16 [B,T,Hq,D], T in 1 … 8 with
+    T * Hq / Hkv <= 64 (G = 16: T <= 4, G = 12: T <= 5), fa2_decode_paged_multi_window_sink_anyg_bf16_plan(...)[2] workspace bytes; for Hq / Hkv
+    in {1, 2, 4, 8} the sibling's bits. window = None: no window. sinks = None: no sink. C entry cln_fa2_decode_paged_multi_window_sink_anyg_bf16
+    (include/cln_amd_ext.h); no CPU path."""
+    _paged_attention("fa2_decode_paged_multi_window_sink_anyg_bf16", torch.bfloat16, 4, fa2_decode_paged_multi_window_sink_anyg_bf16_plan, q,
+                     k_pages, v_pages, block_table, seqlens, None, None, None, out, lse, workspace, _NO_WINDOW if window is None else window, sinks,
+                     True)
+
+
+def fa2_prefill_paged_varlen_window_sink_anyg_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, window, sinks, out,
+                                                       lse=None):
+    """fa2_prefill_paged_varlen_window_sink_bf16_fp8 for any group size Hq / Hkv in 1 … 16: pools, scales, numerics, window = None, sinks = None
+    and errors as there, and for Hq / Hkv in {1, 2, 4, 8} its bits. C entry cln_fa2_prefill_paged_varlen_window_sink_anyg_bf16_fp8
+    (include/cln_amd_ext.h); no CPU path."""
+    _paged_attention("fa2_prefill_paged_varlen_window_sink_anyg_bf16_fp8", torch.bfloat16, 3, None, q, k_pages, v_pages, block_table, seqlens,
+                     cu_q, k_scale, v_scale, out, lse, None, _NO_WINDOW if window is None else window, sinks, True)
+
+
+def fa2_decode_paged_multi_window_sink_anyg_bf16_fp8_plan(B, T, Hq, Hkv, max_pages, page, D, window):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_window_sink_anyg_bf16_fp8: what
+    fa2_decode_paged_multi_window_sink_anyg_bf16_plan returns for the same numbers
+    (cln_fa2_decode_paged_multi_window_sink_anyg_bf16_fp8_plan, include/cln_amd_ext.h). No GPU needed."""
+    return _paged_plan("fa2_decode_paged_multi_window_sink_anyg_bf16_fp8", B, T, Hq, Hkv, max_pages, page, D,
+                       window=_NO_WINDOW if window is None else window)
+
+
+def fa2_decode_paged_multi_window_sink_anyg_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, window, sinks, out, lse=None,
+                                                     workspace=None):
+    """fa2_decode_paged_multi_window_sink_bf16_fp8 for any group size Hq / Hkv in 1 … 16: T in 1 … 8 with T * Hq / Hkv <= 64,
+    fa2_decode_paged_multi_window_sink_anyg_bf16_fp8_plan(...)[2] workspace bytes; everything else as there, and for Hq / Hkv in {1, 2, 4, 8}
+    its bits. C entry cln_fa2_decode_paged_multi_window_sink_anyg_bf16_fp8 (include/cln_amd_ext.h); no CPU path."""
+    _paged_attention("fa2_decode_paged_multi_window_sink_anyg_bf16_fp8", torch.bfloat16, 4, fa2_decode_paged_multi_window_sink_anyg_bf16_fp8_plan,
+                     q, k_pages, v_pages, block_table, seqlens, None, k_scale, v_scale, out, lse, workspace,
+                     _NO_WINDOW if window is None else window, sinks, True)

@@ -635,6 +635,34 @@ def describe_decode_paged_multi_window_sink_bf16_fp8(B, T, Hq, Hkv, max_pages, p
                           2560)
 
 
+def describe_prefill_paged_varlen_window_sink_anyg_bf16(B, total_q, Hq, Hkv, max_pages, page, D, window):
+    """describe() for cln_fa2_prefill_paged_varlen_window_sink_anyg_bf16 (include/cln_amd_ext.h): the text of the sink entry with the any-G kernel,
+    G as a number and where the division stands (no GPU needed). ValueError for an unsupported or invalid shape or window."""
+    return _describe_bf16("cln_fa2_prefill_paged_varlen_window_sink_anyg_bf16",
+                          tuple(int(x) for x in (B, total_q, Hq, Hkv, max_pages, page, D, window)), 2560)
+
+
+def describe_decode_paged_multi_window_sink_anyg_bf16(B, T, Hq, Hkv, max_pages, page, D, window):
+    """describe() for cln_fa2_decode_paged_multi_window_sink_anyg_bf16 (include/cln_amd_ext.h): the text of the sink entry with the any-G kernel,
+    G as a number and where the division stands (no GPU needed). ValueError for an unsupported or invalid shape or window."""
+    return _describe_bf16("cln_fa2_decode_paged_multi_window_sink_anyg_bf16", tuple(int(x) for x in (B, T, Hq, Hkv, max_pages, page, D, window)),
+                          2560)
+
+
+def describe_prefill_paged_varlen_window_sink_anyg_bf16_fp8(B, total_q, Hq, Hkv, max_pages, page, D, window):
+    """describe() for cln_fa2_prefill_paged_varlen_window_sink_anyg_bf16_fp8 (include/cln_amd_ext.h): the text of the FP8 sink entry with the
+    any-G kernel (no GPU needed). ValueError for an unsupported or invalid shape or window."""
+    return _describe_bf16("cln_fa2_prefill_paged_varlen_window_sink_anyg_bf16_fp8",
+                          tuple(int(x) for x in (B, total_q, Hq, Hkv, max_pages, page, D, window)), 3072)
+
+
+def describe_decode_paged_multi_window_sink_anyg_bf16_fp8(B, T, Hq, Hkv, max_pages, page, D, window):
+    """describe() for cln_fa2_decode_paged_multi_window_sink_anyg_bf16_fp8 (include/cln_amd_ext.h): the text of the FP8 sink entry with the
+    any-G kernel (no GPU needed). ValueError for an unsupported or invalid shape or window."""
+    return _describe_bf16("cln_fa2_decode_paged_multi_window_sink_anyg_bf16_fp8",
+                          tuple(int(x) for x in (B, T, Hq, Hkv, max_pages, page, D, window)), 3072)
+
+
 def describe_kv_append_paged_varlen_bf16_fp8(B, total_q, Hq, Hkv, max_pages, page, D, rope_mode):
     """describe() for cln_kv_append_paged_varlen_bf16_fp8 (include/cln_amd_ext.h): the kernel instantiation and the launch as text (no GPU
     needed). rope_mode: 0 / "none", 1 / "half", 2 / "interleaved". ValueError for an unsupported or invalid shape."""

@@ -395,6 +395,55 @@ int cln_fa2_decode_paged_multi_window_sink_bf16_fp8(const void* q, const void* k
 int cln_fa2_decode_paged_multi_window_sink_bf16_fp8_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window, char* buf,
                                                              int len);
 
+/* ---- ANY QUERY-GROUP SIZE G = Hq / Hkv in 1 ... 16 on the bf16 paged attention path: the entries above take
+ * G in {1, 2, 4, 8} only and keep doing so; these four take every integer G from 1 to 16 -- 3 (Llama-3.2-3B), 5, 6, 7 (Qwen2.5), 12, 16
+ * (Llama-3.1-405B, Qwen3-235B) among them. The append entries take any Hq % Hkv == 0 as they are. Each is the most general form: a
+ * full-attention layer passes a window past the cache, a layer without sinks passes sinks = NULL (legal in all four, the bf16 pair included: bit
+ * for bit the result of a [Hq] tensor of -inf).
+ *
+ * cln_fa2_prefill_paged_varlen_window_sink_anyg_bf16 / cln_fa2_decode_paged_multi_window_sink_anyg_bf16: the function, the tensors and the
+ * argument list of the *_window_sink_bf16 entries (section 19). *_anyg_bf16_fp8: those of the *_window_sink_bf16_fp8 entries (section 20). Query
+ * head h reads KV head h / G (integer division); row r = t G + g of a (sequence, KV head) is token t = r / G, head kvh G + g. The kernels divide
+ * (unsigned 32-bit, exact for every row) in front of and behind the key loop, which is the sibling's, statement for statement. For G in
+ * {1, 2, 4, 8}, o and lse are the sibling's bit for bit.
+ * Decode: a workgroup serves the T G rows of a (sequence, KV head) in ceil(T G / 16) <= 4 row tiles, so T <= 8 AND T G <= 64: G = 16 with
+ * T <= 4, G = 12 with T <= 5, G <= 8 with any T <= 8. The prefill has no such limit.
+ * Plan: fa2d::split_plan of (B Hkv, B T Hq, the window entry's span and unit, D) -- for G in {1, 2, 4, 8} cln_fa2_decode_paged_multi_window_bf16_plan,
+ * status included. The workspace is fp32 in the siblings' layout; the splits are merged by the siblings' combine kernels.
+ * Status: that of the sibling for the same arguments in the same order, except: Hq / Hkv in 1 ... 16 is legal and G > 16 is -2; the decode's
+ * T G > 64 is -2 where T > 8 is; sinks == NULL is legal (a misaligned sinks, or sinks equal to an output, stays -1). Hq % Hkv != 0 is -1;
+ * window <= 0 is -1, checked behind the shape. D in {64, 128}, page in {16, 32, 64, 128, 256}.
+ */
+int cln_fa2_prefill_paged_varlen_window_sink_anyg_bf16(const void* q, const void* k_pages, const void* v_pages, const int* block_table,
+                                                       const int* seqlens, const int* cu_q, const float* sinks /* may be NULL */, void* o,
+                                                       float* lse, int B, int total_q, int Hq, int Hkv, int P, int max_pages, int page, int D,
+                                                       int window, void* stream);
+int cln_fa2_prefill_paged_varlen_window_sink_anyg_bf16_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D, int window,
+                                                                char* buf, int len);
+int cln_fa2_decode_paged_multi_window_sink_anyg_bf16_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window, int* splits,
+                                                          int* chunk, long long* workspace_bytes);
+int cln_fa2_decode_paged_multi_window_sink_anyg_bf16(const void* q, const void* k_pages, const void* v_pages, const int* block_table,
+                                                     const int* seqlens, const float* sinks /* may be NULL */, void* o, float* lse,
+                                                     void* workspace, long long workspace_bytes, int B, int T, int Hq, int Hkv, int P,
+                                                     int max_pages, int page, int D, int window, void* stream);
+int cln_fa2_decode_paged_multi_window_sink_anyg_bf16_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window, char* buf,
+                                                              int len);
+int cln_fa2_prefill_paged_varlen_window_sink_anyg_bf16_fp8(const void* q, const void* k_pages, const void* v_pages, const int* block_table,
+                                                           const int* seqlens, const int* cu_q, const float* k_scale, const float* v_scale,
+                                                           const float* sinks /* may be NULL */, void* o, float* lse, int B, int total_q, int Hq,
+                                                           int Hkv, int P, int max_pages, int page, int D, int window, void* stream);
+int cln_fa2_prefill_paged_varlen_window_sink_anyg_bf16_fp8_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D,
+                                                                    int window, char* buf, int len);
+int cln_fa2_decode_paged_multi_window_sink_anyg_bf16_fp8_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window,
+                                                              int* splits, int* chunk, long long* workspace_bytes);
+int cln_fa2_decode_paged_multi_window_sink_anyg_bf16_fp8(const void* q, const void* k_pages, const void* v_pages, const int* block_table,
+                                                         const int* seqlens, const float* k_scale, const float* v_scale,
+                                                         const float* sinks /* may be NULL */, void* o, float* lse, void* workspace,
+                                                         long long workspace_bytes, int B, int T, int Hq, int Hkv, int P, int max_pages, int page,
+                                                         int D, int window, void* stream);
+int cln_fa2_decode_paged_multi_window_sink_anyg_bf16_fp8_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window,
+                                                                  char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
