@@ -344,6 +344,63 @@ def fa2_decode_paged_multi_window_sink_anyg_bf16_fp8_plan(B, T, Hq, Hkv, max_pag
     return host.fa2_decode_paged_multi_window_sink_anyg_bf16_fp8_plan(B, T, Hq, Hkv, max_pages, page, D, window)
 
 
+def fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, window, sinks, softmax_scale, softcap,
+                                                           out, lse=None):
+    """fa2_prefill_paged_varlen_window_sink_anyg_bf16 with a softmax scale (None: 1 / sqrt(D); Gemma-2-27B 144 ** -0.5, Gemma-3-27B 168 ** -0.5,
+    Granite's attention_multiplier) and logit soft-capping cap * tanh(score / cap) (None: no cap; Gemma-2 50, Grok-1 30), capped before the
+    mask, the sink neither scaled nor capped. Both None: the any-G entry's bits. C entry cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16
+    (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, window, sinks,
+                                                                       softmax_scale, softcap, out, lse)
+
+
+def fa2_decode_paged_multi_window_sink_softcap_anyg_bf16(q, k_pages, v_pages, block_table, seqlens, window, sinks, softmax_scale, softcap, out,
+                                                         lse=None, workspace=None):
+    """fa2_decode_paged_multi_window_sink_anyg_bf16 with a softmax scale and logit soft-capping (as for
+    fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16). C entry cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16
+    (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_decode_paged_multi_window_sink_softcap_anyg_bf16(q, k_pages, v_pages, block_table, seqlens, window, sinks, softmax_scale,
+                                                                     softcap, out, lse, workspace)
+
+
+def fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_window_sink_softcap_anyg_bf16: what
+    fa2_decode_paged_multi_window_sink_anyg_bf16_plan returns; window = None: no window. C entry
+    cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_plan."""
+    from . import host
+    return host.fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window)
+
+
+def fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, window, sinks,
+                                                               softmax_scale, softcap, out, lse=None):
+    """fa2_prefill_paged_varlen_window_sink_anyg_bf16_fp8 with a softmax scale and logit soft-capping (as for
+    fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16; k_scale inside the tanh). C entry
+    cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16_fp8 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, window,
+                                                                           sinks, softmax_scale, softcap, out, lse)
+
+
+def fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, window, sinks,
+                                                             softmax_scale, softcap, out, lse=None, workspace=None):
+    """fa2_decode_paged_multi_window_sink_anyg_bf16_fp8 with a softmax scale and logit soft-capping (as for
+    fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16; k_scale inside the tanh). C entry
+    cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, window, sinks,
+                                                                         softmax_scale, softcap, out, lse, workspace)
+
+
+def fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_plan(B, T, Hq, Hkv, max_pages, page, D, window):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8: what
+    fa2_decode_paged_multi_window_sink_anyg_bf16_plan returns; window = None: no window. C entry
+    cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_plan."""
+    from . import host
+    return host.fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_plan(B, T, Hq, Hkv, max_pages, page, D, window)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

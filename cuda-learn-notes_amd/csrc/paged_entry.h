@@ -194,6 +194,48 @@ inline int multi_window_plan_anyg(int B, int T, int Hq, int Hkv, int max_pages, 
 }
 // multi_tiles serves it as it is: ceil(T G / 16), 1 ... 4
 
+// ---------------------------------------------------------------- softmax scale and logit soft-capping (the *_softcap_* entries)
+// The two floats of a *_softcap_* entry, checked before anything else is looked at: softmax_scale == 0 means 1 / sqrt(D), softcap == 0 means no
+// cap; any other value is finite and > 0, else -1 (a NaN fails every comparison). With x = the scale in use, what the kernels take:
+//   mult  x log2(e): the score multiplier without a cap, and with one the multiplier of the small-argument branch (cap2 y = q.k mult). For
+//         softmax_scale == 0 it is fa2d::scale_log2(D) itself, the number the siblings pass, else (float)((double)softmax_scale log2(e)).
+//   pre   2 log2(e) x / cap: q.k pre = 2 log2(e) y is the exponent of exp2 in tanh(y) = 1 - 2 / (1 + e^(2 y)), y = q.k x / cap
+//   cap2  cap log2(e): the capped score in the log2 units of the softmax
+// mult and pre are clamped to FLT_MAX, cap2 to half of it: 0 times either stays 0. D <= 0 is the shape check's to refuse; no number is formed from it here.
+struct SoftCap {
+  float mult, pre, cap2;
+  bool cap;
+};
+inline int softcap_arg(float softmax_scale, float softcap, int D, SoftCap* s) {
+  if (!(softmax_scale >= 0.0f) || !(softcap >= 0.0f) || std::isinf(softmax_scale) || std::isinf(softcap)) return CLN_ERR_BAD_ARG;
+  constexpr double kLog2e = 1.4426950408889634, kMax = 3.4028234663852886e38;
+  const double x = softmax_scale != 0.0f ? (double)softmax_scale : D > 0 ? 1.0 / sqrt((double)D) : 1.0;
+  const double mult = x * kLog2e;
+  s->cap = softcap != 0.0f;
+  s->mult = softmax_scale != 0.0f ? (float)(mult < kMax ? mult : kMax) : D > 0 ? fa2d::scale_log2(D) : 1.0f;
+  const double pre = s->cap ? 2.0 * mult / (double)softcap : 0.0;
+  s->pre = (float)(pre < kMax ? pre : kMax);
+  const double cap2 = (double)softcap * kLog2e;
+  s->cap2 = (float)(cap2 < kMax / 2 ? cap2 : kMax / 2);  // the kernels form 2 cap2
+  return CLN_OK;
+}
+// The head of a *_softcap_* describe text, in front of the any-G sibling's text: the kernel, the scale in use and, with a cap, the cap clause --
+// where the cap sits relative to the mask and the sink. Returns the characters written (< len), or len - 1 when the text did not fit.
+inline int softcap_describe(char* buf, int len, const char* kernel, int D, float softmax_scale, float softcap, const SoftCap& s, bool fp8) {
+  int n = snprintf(buf, len, "%s<D=%d,CAP=%d> softmax_scale=%.9g (%s), score multiplier x log2(e) = %.9g%s; ", kernel, D, s.cap ? 1 : 0,
+                   softmax_scale != 0.0f ? (double)softmax_scale : 1.0 / sqrt((double)D),
+                   softmax_scale != 0.0f ? "the caller's" : "the default 1 / sqrt(D)", (double)s.mult, fp8 ? " times k_scale" : "");
+  if (n < len && s.cap)
+    n += snprintf(buf + n, len - n,
+                  "softcap=%.9g: every score is cap tanh(q.k x / cap)%s in fp32 (1 - 2 / (1 + exp2) on v_exp_f32 and v_rcp_f32; below |q.k x / cap| "
+                  "= 2^-5 the series q.k x (1 - y^2 / 3)), capped before the window and causal mask (a hidden key is -inf, not -cap), the sink "
+                  "neither scaled nor capped; ",
+                  (double)softcap, fp8 ? " with k_scale inside the tanh" : "");
+  if (n < len && !s.cap) n += snprintf(buf + n, len - n, "no cap: the any-G body with this multiplier; ");
+  if (n < len) n += snprintf(buf + n, len - n, "otherwise ");
+  return n < len ? n : len - 1;
+}
+
 // The arguments of a decode entry in the order of their status codes: the pointers (fa2d::check_pointers), P, the status of the entry's plan
 // and, where the plan splits the keys, the workspace. The *_sink_* entries put their fp32 sinks [Hq] last in `in`, behind seqlens.
 inline int decode_args(const void* const* in, int n_in, const void* const (&out)[3], long long workspace_bytes, int P, int plan_rc,

@@ -11,6 +11,7 @@ Reference bindings mirrored (checks and messages):
   head-dim switch default  -> RuntimeError("headdim not support!")           flash_attn_mma_share_qkv.cu:860,:882
 """
 import ctypes
+import math
 import os
 import threading
 import types
@@ -808,12 +809,13 @@ def _paged_plan(name, *dims, window=None):
 
 
 def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, out, lse, workspace,
-                     window=None, sinks=None, sinks_optional=False):
+                     window=None, sinks=None, sinks_optional=False, floats=()):
     """The body of every attention entry over a paged cache. q, out: dtype [B,Hq,D] (q_dims = 3) or [B,T,Hq,D] (4), or with cu_q the packed
     [total_q,Hq,D]; the pools hold dtype, or with k_scale / v_scale e4m3; plan = the *_plan of a decode entry, which splits the keys and takes
     a workspace, or None for a prefill entry: one launch, and what cannot be launched is told here, in the words of the plan. window = the W of
     a sliding-window entry: one more int behind D, for the entry and its plan. sinks = the fp32 [Hq] of a *_sink_* entry: the last input pointer;
-    sinks_optional: the entry has that pointer and takes NULL for sinks = None."""
+    sinks_optional: the entry has that pointer and takes NULL for sinks = None. floats = the (softmax_scale, softcap) of a *_softcap_* entry
+    (_paged_softcap): two floats behind the window, for the entry but not for its plan."""
     packed, fp8, sink = cu_q is not None, k_scale is not None, sinks is not None
     sink_ptr = sink or sinks_optional
     win = _paged_window(name, window)
@@ -821,7 +823,7 @@ def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table
         _paged_sinks(sinks, q)
     fn = _lse_fns.get("cln_" + name) or _ext_fn(  # the prototype is put together on the first call only
         "cln_" + name, [ctypes.c_void_p] * (7 + packed + 2 * fp8 + sink_ptr) + ([ctypes.c_void_p, ctypes.c_longlong] if plan else [])
-        + [ctypes.c_int] * (q_dims + 4 + packed + len(win)) + [ctypes.c_void_p])
+        + [ctypes.c_int] * (q_dims + 4 + packed + len(win)) + [ctypes.c_float] * len(floats) + [ctypes.c_void_p])
     _decode_check((q, out) if fp8 else (q, k_pages, v_pages, out), (block_table, seqlens, cu_q) if packed else (block_table, seqlens), dtype)
     if sink:
         _check_dev(sinks)
@@ -859,7 +861,7 @@ def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table
     if sink_ptr:
         more += (sinks.data_ptr() if sink else None,)
     rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), *more, out.data_ptr(),
-            None if lse is None else lse.data_ptr(), *ws, *((B, *lead) if packed else lead), Hkv, P, max_pages, page, D, *win, _stream())
+            None if lse is None else lse.data_ptr(), *ws, *((B, *lead) if packed else lead), Hkv, P, max_pages, page, D, *win, *floats, _stream())
     _raise(name, rc, too_large)
 
 
@@ -1263,3 +1265,79 @@ def fa2_decode_paged_multi_window_sink_anyg_bf16_fp8(q, k_pages, v_pages, block_
     _paged_attention("fa2_decode_paged_multi_window_sink_anyg_bf16_fp8", torch.bfloat16, 4, fa2_decode_paged_multi_window_sink_anyg_bf16_fp8_plan,
                      q, k_pages, v_pages, block_table, seqlens, None, k_scale, v_scale, out, lse, workspace,
                      _NO_WINDOW if window is None else window, sinks, True)
+
+
+def _paged_softcap(name, softmax_scale, softcap):
+    """The two floats of a *_softcap_* entry: None is the C entry's 0 -- softmax_scale: 1 / sqrt(D), softcap: no cap; a 0 given as
+    a number means the same -- and any other value is finite and > 0."""
+    out = []
+    for what, v in (("softmax_scale", softmax_scale), ("softcap", softcap)):
+        if v is None:
+            out.append(0.0)
+            continue
+        v = float(v)
+        if not (0.0 <= v < math.inf):
+            raise RuntimeError("%s: %s %r not supported (finite and > 0, or None)" % (name, what, v))
+        out.append(v)
+    return tuple(out)
+
+
+def fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, window, sinks, softmax_scale, softcap,
+                                                           out, lse=None):
+    """fa2_prefill_paged_varlen_window_sink_anyg_bf16 with a softmax scale and logit soft-capping: the score of a key is u = q.k * softmax_scale
+    (None: 1 / sqrt(D)) and, with softcap = c, c * tanh(u / c) (None: no cap), capped before the window and causal mask; the sink is neither
+    scaled nor capped. Both None: the bits of fa2_prefill_paged_varlen_window_sink_anyg_bf16. Everything else as there. C entry
+    cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16"
+    _paged_attention(name, torch.bfloat16, 3, None, q, k_pages, v_pages, block_table, seqlens, cu_q, None, None, out, lse, None,
+                     _NO_WINDOW if window is None else window, sinks, True, _paged_softcap(name, softmax_scale, softcap))
+
+
+def fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_window_sink_softcap_anyg_bf16: what
+    fa2_decode_paged_multi_window_sink_anyg_bf16_plan returns for the same numbers -- neither the scale nor the cap changes the splits or the
+    workspace (cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_plan, include/cln_amd_ext.h). No GPU needed."""
+    return _paged_plan("fa2_decode_paged_multi_window_sink_softcap_anyg_bf16", B, T, Hq, Hkv, max_pages, page, D,
+                       window=_NO_WINDOW if window is None else window)
+
+
+def fa2_decode_paged_multi_window_sink_softcap_anyg_bf16(q, k_pages, v_pages, block_table, seqlens, window, sinks, softmax_scale, softcap, out,
+                                                         lse=None, workspace=None):
+    """fa2_decode_paged_multi_window_sink_anyg_bf16 with a softmax scale and logit soft-capping (softmax_scale, softcap as for
+    fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16; both None: the bits of fa2_decode_paged_multi_window_sink_anyg_bf16);
+    fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_plan(...)[2] workspace bytes. C entry
+    cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "fa2_decode_paged_multi_window_sink_softcap_anyg_bf16"
+    _paged_attention(name, torch.bfloat16, 4, fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_plan, q, k_pages, v_pages, block_table, seqlens,
+                     None, None, None, out, lse, workspace, _NO_WINDOW if window is None else window, sinks, True,
+                     _paged_softcap(name, softmax_scale, softcap))
+
+
+def fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, window, sinks,
+                                                               softmax_scale, softcap, out, lse=None):
+    """fa2_prefill_paged_varlen_window_sink_anyg_bf16_fp8 with a softmax scale and logit soft-capping (softmax_scale, softcap as for
+    fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16); k_scale is part of the dequantised score and stands inside the tanh. C entry
+    cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16_fp8 (include/cln_amd_ext.h); no CPU path."""
+    name = "fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16_fp8"
+    _paged_attention(name, torch.bfloat16, 3, None, q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, out, lse, None,
+                     _NO_WINDOW if window is None else window, sinks, True, _paged_softcap(name, softmax_scale, softcap))
+
+
+def fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_plan(B, T, Hq, Hkv, max_pages, page, D, window):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8: what
+    fa2_decode_paged_multi_window_sink_anyg_bf16_plan returns for the same numbers
+    (cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_plan, include/cln_amd_ext.h). No GPU needed."""
+    return _paged_plan("fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8", B, T, Hq, Hkv, max_pages, page, D,
+                       window=_NO_WINDOW if window is None else window)
+
+
+def fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8(q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, window, sinks,
+                                                             softmax_scale, softcap, out, lse=None, workspace=None):
+    """fa2_decode_paged_multi_window_sink_anyg_bf16_fp8 with a softmax scale and logit soft-capping (softmax_scale, softcap as for
+    fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16; k_scale inside the tanh);
+    fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_plan(...)[2] workspace bytes. C entry
+    cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8 (include/cln_amd_ext.h); no CPU path."""
+    name = "fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8"
+    _paged_attention(name, torch.bfloat16, 4, fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_plan, q, k_pages, v_pages, block_table,
+                     seqlens, None, k_scale, v_scale, out, lse, workspace, _NO_WINDOW if window is None else window, sinks, True,
+                     _paged_softcap(name, softmax_scale, softcap))

@@ -561,16 +561,18 @@ def describe_kv_append_paged_varlen(B, total_q, Hq, Hkv, max_pages, page, D, rop
     return buf.value.decode()
 
 
-def _describe_bf16(cname, dims, size=1280):
-    """The text of the bf16 paged entry `cname`_describe for the int tuple dims; ValueError for an unsupported or invalid shape."""
+def _describe_bf16(cname, dims, size=1280, floats=()):
+    """The text of the bf16 paged entry `cname`_describe for the int tuple dims (and, for a *_softcap_* entry, the two floats behind them);
+    ValueError for an unsupported or invalid shape."""
     import ctypes
     from . import _loader
     fn = getattr(_loader.load_so("libcln_amd.so"), cname + "_describe")
-    fn.argtypes, fn.restype = [ctypes.c_int] * len(dims) + [ctypes.c_char_p, ctypes.c_int], ctypes.c_int
+    fn.argtypes = [ctypes.c_int] * len(dims) + [ctypes.c_float] * len(floats) + [ctypes.c_char_p, ctypes.c_int]
+    fn.restype = ctypes.c_int
     buf = ctypes.create_string_buffer(size)
-    rc = fn(*dims, buf, size)
+    rc = fn(*dims, *floats, buf, size)
     if rc < 0:
-        raise ValueError("%s: shape %s not supported (status %d)" % (cname, dims, rc))
+        raise ValueError("%s: shape %s not supported (status %d)" % (cname, tuple(dims) + tuple(floats), rc))
     return buf.value.decode()
 
 
@@ -661,6 +663,42 @@ def describe_decode_paged_multi_window_sink_anyg_bf16_fp8(B, T, Hq, Hkv, max_pag
     any-G kernel (no GPU needed). ValueError for an unsupported or invalid shape or window."""
     return _describe_bf16("cln_fa2_decode_paged_multi_window_sink_anyg_bf16_fp8",
                           tuple(int(x) for x in (B, T, Hq, Hkv, max_pages, page, D, window)), 3072)
+
+
+def _describe_softcap(cname, dims, softmax_scale, softcap):
+    """describe() of a *_softcap_* entry: None is the C entry's 0 for either float."""
+    floats = tuple(0.0 if x is None else float(x) for x in (softmax_scale, softcap))
+    return _describe_bf16(cname, tuple(int(x) for x in dims), 4096, floats)
+
+
+def describe_prefill_paged_varlen_window_sink_softcap_anyg_bf16(B, total_q, Hq, Hkv, max_pages, page, D, window, softmax_scale=None, softcap=None):
+    """describe() for cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16 (include/cln_amd_ext.h): the kernel instantiation, the softmax
+    scale in use, with a cap where it sits relative to the mask and the sink, then the any-G entry's text (no GPU needed). ValueError for an
+    unsupported or invalid shape, window, scale or cap."""
+    return _describe_softcap("cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16", (B, total_q, Hq, Hkv, max_pages, page, D, window),
+                             softmax_scale, softcap)
+
+
+def describe_decode_paged_multi_window_sink_softcap_anyg_bf16(B, T, Hq, Hkv, max_pages, page, D, window, softmax_scale=None, softcap=None):
+    """describe() for cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16 (include/cln_amd_ext.h): as for the prefill entry, with the split
+    plan of the any-G entry's text (no GPU needed). ValueError for an unsupported or invalid shape, window, scale or cap."""
+    return _describe_softcap("cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16", (B, T, Hq, Hkv, max_pages, page, D, window), softmax_scale,
+                             softcap)
+
+
+def describe_prefill_paged_varlen_window_sink_softcap_anyg_bf16_fp8(B, total_q, Hq, Hkv, max_pages, page, D, window, softmax_scale=None,
+                                                                    softcap=None):
+    """describe() for cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16_fp8 (include/cln_amd_ext.h): the FP8 form, k_scale inside the tanh
+    (no GPU needed). ValueError for an unsupported or invalid shape, window, scale or cap."""
+    return _describe_softcap("cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16_fp8", (B, total_q, Hq, Hkv, max_pages, page, D, window),
+                             softmax_scale, softcap)
+
+
+def describe_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8(B, T, Hq, Hkv, max_pages, page, D, window, softmax_scale=None, softcap=None):
+    """describe() for cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8 (include/cln_amd_ext.h): the FP8 form, k_scale inside the tanh
+    (no GPU needed). ValueError for an unsupported or invalid shape, window, scale or cap."""
+    return _describe_softcap("cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8", (B, T, Hq, Hkv, max_pages, page, D, window),
+                             softmax_scale, softcap)
 
 
 def describe_kv_append_paged_varlen_bf16_fp8(B, total_q, Hq, Hkv, max_pages, page, D, rope_mode):

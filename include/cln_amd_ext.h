@@ -444,6 +444,55 @@ int cln_fa2_decode_paged_multi_window_sink_anyg_bf16_fp8(const void* q, const vo
 int cln_fa2_decode_paged_multi_window_sink_anyg_bf16_fp8_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window,
                                                                   char* buf, int len);
 
+/* ---- SOFTMAX SCALE AND LOGIT SOFT-CAPPING on the bf16 paged attention path: the entries above fix the softmax scale
+ * at 1 / sqrt(D) and have no soft-capping, and keep doing so; these four are the any-G entries with two floats behind `window`. Gemma-2-27B
+ * (D = 128, query_pre_attn_scalar 144, cap 50), Gemma-3-27B (168, no cap), Granite (attention_multiplier) and Grok-1 (G = 6, cap 30) need them.
+ *
+ * With x = softmax_scale, or 1 / sqrt(D) when softmax_scale == 0, a row of head h that sees the keys lo <= j < n has u_j = q.k_j x and
+ *   s_j = u_j                        softcap == 0: no cap
+ *   s_j = softcap tanh(u_j / softcap)  otherwise
+ *   O = sum_j exp(s_j) v_j / (sum_j exp(s_j) + exp(sink_h)),  LSE = ln of that denominator.
+ * The sink is neither scaled nor capped. The window and causal mask are applied after the cap: a hidden key is -inf, not -softcap. A row that
+ * sees no key stays O = 0, LSE = -inf. FP8 pools: k_scale[kv head] is part of the dequantised score and stands inside the tanh; v_scale stays in
+ * the normalisation.
+ * softmax_scale: 0 means 1 / sqrt(D), with the multiplier the any-G entries pass; any other value is finite and > 0 and the score multiplier is
+ * (float)((double)softmax_scale log2(e)). softcap: 0 means no cap, and the kernel that runs is the any-G body; any other value is finite and > 0.
+ * With both 0, o and lse are the any-G entries' bit for bit. A negative, NaN or infinite value of either is -1, checked before anything else --
+ * no pointer is looked at. Every other argument, check and status code is the any-G entry's, in its order. The _describe entries take both floats
+ * and check them the same way; the _plan entries take neither: the plan of the any-G entry for the same numbers.
+ */
+int cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16(const void* q, const void* k_pages, const void* v_pages, const int* block_table,
+                                                               const int* seqlens, const int* cu_q, const float* sinks /* may be NULL */, void* o,
+                                                               float* lse, int B, int total_q, int Hq, int Hkv, int P, int max_pages, int page,
+                                                               int D, int window, float softmax_scale, float softcap, void* stream);
+int cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D,
+                                                                        int window, float softmax_scale, float softcap, char* buf, int len);
+int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window,
+                                                                  int* splits, int* chunk, long long* workspace_bytes);
+int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16(const void* q, const void* k_pages, const void* v_pages, const int* block_table,
+                                                             const int* seqlens, const float* sinks /* may be NULL */, void* o, float* lse,
+                                                             void* workspace, long long workspace_bytes, int B, int T, int Hq, int Hkv, int P,
+                                                             int max_pages, int page, int D, int window, float softmax_scale, float softcap,
+                                                             void* stream);
+int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window,
+                                                                      float softmax_scale, float softcap, char* buf, int len);
+int cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16_fp8(const void* q, const void* k_pages, const void* v_pages, const int* block_table,
+                                                                   const int* seqlens, const int* cu_q, const float* k_scale,
+                                                                   const float* v_scale, const float* sinks /* may be NULL */, void* o, float* lse,
+                                                                   int B, int total_q, int Hq, int Hkv, int P, int max_pages, int page, int D,
+                                                                   int window, float softmax_scale, float softcap, void* stream);
+int cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16_fp8_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D,
+                                                                            int window, float softmax_scale, float softcap, char* buf, int len);
+int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window,
+                                                                      int* splits, int* chunk, long long* workspace_bytes);
+int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8(const void* q, const void* k_pages, const void* v_pages, const int* block_table,
+                                                                 const int* seqlens, const float* k_scale, const float* v_scale,
+                                                                 const float* sinks /* may be NULL */, void* o, float* lse, void* workspace,
+                                                                 long long workspace_bytes, int B, int T, int Hq, int Hkv, int P, int max_pages,
+                                                                 int page, int D, int window, float softmax_scale, float softcap, void* stream);
+int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D,
+                                                                          int window, float softmax_scale, float softcap, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
