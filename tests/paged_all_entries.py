@@ -1,5 +1,5 @@
 """Every entry of the paged KV-cache path behind one calling convention, for the tests that run ALL of them (tests/test_gpu_paged_large_pool.py,
-tests/test_gpu_paged_unaligned_operands.py): the 15 attention entries (fa2_decode_paged*, fa2_prefill_paged*) and the 5 append entries
+tests/test_gpu_paged_unaligned_operands.py): the 23 attention entries (fa2_decode_paged*, fa2_prefill_paged*) and the 5 append entries
 (kv_append_paged*), one small case per entry from the builders the families' own tests use (paged_decode_reference.make_pool,
 fp8_kv_reference.make_pool, paged_bf16_fp8_reference.quantize_pools, paged_sink_reference.sinks_mixed), and the check of a result against the
 family's fp64 reference with the family's own check function and bound -- no tolerance is defined here:
@@ -7,7 +7,11 @@ family's fp64 reference with the family's own check function and bound -- no tol
     fp16 over e4m3    the check() of tests/test_gpu_fa2_decode_paged_fp8.py and fp8_paged_attn_cases.Entry.check
     bf16 (over e4m3)  paged_sink_reference (paged_bf16_fp8_reference) .prefill / .decode, held by the check() of
                       tests/test_gpu_paged_sink_attention.py; an entry without sinks is that reference with sinks of -inf, one without a window
-                      that reference with W = None, which is how paged_bf16_fp8_reference already treats sinks = None.
+                      that reference with W = None, which is how paged_bf16_fp8_reference already treats sinks = None. The *_anyg_* entries run
+                      with G = Hq / Hkv = 3, which their power-of-two siblings refuse, against the same references (both index the KV head as
+                      h // G).
+    *_softcap_anyg_*  paged_softcap_reference.prefill / .decode with the scale and the cap of its sensitive cases (scale_for(D), CAP = 2, q x 4:
+                      most scores sit past the cap), held by the same check(), as tests/test_gpu_paged_softcap_attention.py does.
 The 4-byte operand sets are those of csrc/paged_entry.h (prefill_args, append_args) and fa2d::check_pointers: everything behind q and the pools
 in a decode entry; that and lse in a prefill entry; every int32 / fp32 input of an append entry, the rope table among them. They agree with the
 `for i in (...)  # ... 4-byte alignment` lists of the surface tests. A plain module: nothing here is collected."""
@@ -21,6 +25,7 @@ import fp8_paged_attn_cases as cs
 import paged_bf16_fp8_reference as b8
 import paged_decode_reference as pr
 import paged_sink_reference as sr
+import paged_softcap_reference as cr
 import test_gpu_fa2_decode_paged as t_dec
 import test_gpu_fa2_decode_paged_fp8 as t_dec8
 import test_gpu_fa2_decode_paged_multi as t_multi
@@ -32,8 +37,9 @@ BF, HALF, F8 = torch.bfloat16, torch.float16, f8.F8
 PAGE = 16
 NEG_INF = float("-inf")
 
-# form: "single" q [B,Hq,D]; "multi" / "prefill" q [B,T,Hq,D]; "varlen" q packed [total_q,Hq,D] with cu_q. plan: a decode entry (splits, workspace)
-Attn = collections.namedtuple("Attn", "name bf16 fp8 form window sink plan")
+# form: "single" q [B,Hq,D]; "multi" / "prefill" q [B,T,Hq,D]; "varlen" q packed [total_q,Hq,D] with cu_q. plan: a decode entry (splits, workspace).
+# anyg: any Hq / Hkv in 1 ... 16 (the case takes ANYG); softcap: softmax_scale and softcap follow the sinks
+Attn = collections.namedtuple("Attn", "name bf16 fp8 form window sink plan anyg softcap", defaults=(False, False))
 ATTN = [
     Attn("fa2_decode_paged", False, False, "single", False, False, True),
     Attn("fa2_decode_paged_multi", False, False, "multi", False, False, True),
@@ -50,6 +56,14 @@ ATTN = [
     Attn("fa2_decode_paged_multi_window_sink_bf16", True, False, "multi", True, True, True),
     Attn("fa2_prefill_paged_varlen_window_sink_bf16_fp8", True, True, "varlen", True, True, False),
     Attn("fa2_decode_paged_multi_window_sink_bf16_fp8", True, True, "multi", True, True, True),
+    Attn("fa2_prefill_paged_varlen_window_sink_anyg_bf16", True, False, "varlen", True, True, False, True),
+    Attn("fa2_decode_paged_multi_window_sink_anyg_bf16", True, False, "multi", True, True, True, True),
+    Attn("fa2_prefill_paged_varlen_window_sink_anyg_bf16_fp8", True, True, "varlen", True, True, False, True),
+    Attn("fa2_decode_paged_multi_window_sink_anyg_bf16_fp8", True, True, "multi", True, True, True, True),
+    Attn("fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16", True, False, "varlen", True, True, False, True, True),
+    Attn("fa2_decode_paged_multi_window_sink_softcap_anyg_bf16", True, False, "multi", True, True, True, True, True),
+    Attn("fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16_fp8", True, True, "varlen", True, True, False, True, True),
+    Attn("fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8", True, True, "multi", True, True, True, True, True),
 ]
 Append = collections.namedtuple("Append", "name bf16 fp8 varlen")
 APPEND = [
@@ -63,6 +77,7 @@ BY_NAME = {e.name: e for e in ATTN + APPEND}
 ROPES = ("none", "half", "interleaved")
 VARLEN_T = [7, 2]
 WINDOW, SPLIT_WINDOW = 65, 5000  # the split case's window covers its 4096 keys: every live page is read, and the plan still splits
+GROUP, ANYG = 4, 3               # Hq / Hkv of a case; the any-G entries take one that is no power of two, so their rows divide by G
 
 
 def pkg():
@@ -98,9 +113,11 @@ def live_entries(bt, lens, page=PAGE):
 def attn_case(name, D, T=1, split=False):
     """The CPU tensors of one small case, made once and never modified. split: B = 1, Hkv = 1, max_pages page = 16384, len 4096 (the plan of every
     decode entry splits it); else B = 2, Hkv = 2, Hq = 8, lengths [9 page + 3, 4 page + 5]: 15 live pages, the second sequence's table has a
-    tail of dead entries."""
+    tail of dead entries. An any-G entry has G = 3 (Hq = 6, or 3 with split); a soft-cap entry has q x 4 under the scale and the cap of
+    softcap_of(): a cap that acts."""
     e = BY_NAME[name]
-    B, Hkv, G, mp, lens = (1, 1, 4, 1024, [4096]) if split else (2, 2, 4, 12, [9 * PAGE + 3, 4 * PAGE + 5])
+    G = ANYG if e.anyg else GROUP
+    B, Hkv, mp, lens = (1, 1, 1024, [4096]) if split else (2, 2, 12, [9 * PAGE + 3, 4 * PAGE + 5])
     Hq, dt = Hkv * G, elem_type(e)
     g = torch.Generator().manual_seed(len(name) + 7 * D + 131 * T + split)
     cu = None
@@ -114,6 +131,8 @@ def attn_case(name, D, T=1, split=False):
         q = torch.randn(cu[-1], Hq, D, generator=g).to(dt)
     else:
         q = torch.randn(B, T, Hq, D, generator=g).to(dt)
+    if e.softcap:
+        q = (q.float() * cr.Q_MUL).to(dt)  # a power of two: exact
     k, v = (torch.randn(B, Hkv, mp * PAGE, D, generator=g) for _ in range(2))
     ks = vs = None
     if e.fp8 and not e.bf16:
@@ -127,6 +146,12 @@ def attn_case(name, D, T=1, split=False):
     W = (SPLIT_WINDOW if split else WINDOW) if e.window else None
     sinks = sr.sinks_mixed(Hq, min(W, lens[0])) if e.sink else None
     return dict(e=e, D=D, T=T, B=B, Hq=Hq, Hkv=Hkv, mp=mp, q=q, kp=kp, vp=vp, bt=bt, lens=lens, cu=cu, ks=ks, vs=vs, W=W, sinks=sinks)
+
+
+def softcap_of(e, D):
+    """(softmax_scale, softcap) every case of a soft-cap entry runs with: the sensitive pair of paged_softcap_reference, neither the default
+    scale nor a cap that does nothing; () for every other entry."""
+    return (cr.scale_for(D), cr.CAP) if e.softcap else ()
 
 
 def to_dev(c, dev):
@@ -161,6 +186,8 @@ def call(e, d, W, o, lse, workspace=None):
         a.append(W)
     if e.sink:
         a.append(d["sinks"])
+    if e.softcap:
+        a += list(softcap_of(e, d["q"].shape[-1]))  # two floats, passed by value: no operand to align
     a += [o, lse]
     if e.plan:
         a.append(workspace)
@@ -178,7 +205,15 @@ def run(e, d, W):
 def check_small(c, o, lse, what):
     """The result (CPU tensors) of the case on its own small pool against the family's fp64 reference, with the family's check and bound."""
     e, q, kp, vp, bt, lens = c["e"], c["q"], c["kp"], c["vp"], c["bt"], c["lens"]
-    if e.bf16:
+    if e.softcap:
+        scale, cap = softcap_of(e, c["D"])
+        kw = dict(ks=c["ks"], vs=c["vs"]) if e.fp8 else {}
+        if e.form == "varlen":
+            ref = cr.prefill(q, kp, vp, bt, lens, c["cu"], c["W"], c["sinks"], scale, cap, **kw)
+        else:
+            ref = cr.decode(q, kp, vp, bt, lens, c["W"], c["sinks"], scale, cap, **kw)
+        t_sink.check(o, lse, *ref, what)
+    elif e.bf16:
         sinks = c["sinks"] if e.sink else torch.full((c["Hq"],), NEG_INF, dtype=torch.float32)
         if e.form == "varlen":
             ref = b8.prefill(q, kp, vp, bt, lens, c["cu"], c["ks"], c["vs"], c["W"], sinks) if e.fp8 else sr.prefill(q, kp, vp, bt, lens, c["cu"], c["W"], sinks)

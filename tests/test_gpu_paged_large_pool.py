@@ -1,4 +1,5 @@
-"""GPU: every entry of the paged KV-cache path over pools of more than 2^32 elements (2^33 bytes). The pool offset
+"""GPU: every entry of the paged KV-cache path -- 23 attention entries, the *_anyg_* and *_softcap_anyg_* ones at G = 3, whose kernels divide
+by the group where their siblings shift, and 5 append entries -- over pools of more than 2^32 elements (2^33 bytes). The pool offset
 ((pg Hkv + kvh) page + row) D + off of PagedKV::elem (csrc/flash_attn_decode_common.cuh, flash_attn_decode_paged_fp8.cuh, paged_bf16.cuh) and of
 the `row` of the five append kernels is formed in 64 bits by casts that no other test holds up: the largest pool elsewhere is a few MiB.
 

@@ -6,8 +6,8 @@ but the rope table, which the append kernels read as 16-byte vectors of a type t
 
 Each shifted operand is a copy at base + 4 bytes of a 16-byte aligned buffer. A run with all of them shifted, and one run per operand shifted
 alone, must give the bits of the aligned run: O and LSE, or the pools and q_out after an append. A shifted lse lies inside a larger filled
-buffer whose words on either side keep their fill. One case per entry from tests/paged_all_entries.py, and a several-splits case of the sink
-decode entries, whose combine kernel reads sinks and seqlens."""
+buffer whose words on either side keep their fill. One case per entry from tests/paged_all_entries.py -- 23 attention entries, the *_anyg_* and
+*_softcap_anyg_* ones at G = 3 -- and a several-splits case of the six sink decode entries, whose combine kernel reads sinks and seqlens."""
 import os
 import sys
 
@@ -88,7 +88,7 @@ def test_attention_with_operands_at_4_byte_alignment(built, dev, name, D):
 
 
 @pytest.mark.parametrize("D", DS)
-@pytest.mark.parametrize("name", ["fa2_decode_paged_multi_window_sink_bf16", "fa2_decode_paged_multi_window_sink_bf16_fp8"])
+@pytest.mark.parametrize("name", [e.name for e in ae.ATTN if e.plan and e.sink])  # the sink pair and its any-G and soft-cap forms (G = 3)
 def test_sink_decode_with_several_splits_reads_sinks_and_lengths_in_the_combine(built, dev, name, D):
     attention(dev, name, D, 1, True)
 

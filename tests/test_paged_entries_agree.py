@@ -26,6 +26,12 @@ DESCRIBE = {
     "packed append": (("kv_append_paged_varlen", "kv_append_paged_varlen_bf16"), True),
 }
 MULTI = DESCRIBE["multi-token decode"][0]
+# the windowed multi-token decode plans, cln_<name>_plan(B, T, Hq, Hkv, max_pages, page, D, window, ...): one definition for all seven; the
+# any-G forms take every Hq / Hkv in 1 ... 16 with T Hq / Hkv <= 64, and where the power-of-two forms accept they return the same plan
+WINDOW_POW2 = ("fa2_decode_paged_multi_window_bf16", "fa2_decode_paged_multi_window_sink_bf16", "fa2_decode_paged_multi_window_sink_bf16_fp8")
+WINDOW_ANYG = ("fa2_decode_paged_multi_window_sink_anyg_bf16", "fa2_decode_paged_multi_window_sink_anyg_bf16_fp8",
+               "fa2_decode_paged_multi_window_sink_softcap_anyg_bf16", "fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8")
+WINDOWS = (0, 1, 65, 300, 2 ** 31 - 1)
 
 
 def _shapes():
@@ -76,3 +82,29 @@ def test_multi_plan_siblings_return_the_same_status_and_plan(lib):
         seen_ok += got[0][0] == 0
         seen_split += got[0][0] == 0 and got[0][1] > 1
     assert seen_ok and seen_split  # plans with one split and with several were compared
+
+
+def test_window_plan_siblings_return_the_same_status_and_plan(lib):
+    def plans(names, dims):
+        got = []
+        for n in names:
+            fn = getattr(lib, "cln_%s_plan" % n)
+            fn.argtypes, fn.restype = [ctypes.c_int] * 8 + [ctypes.c_void_p] * 3, ctypes.c_int
+            s, c, w = ctypes.c_int(-7), ctypes.c_int(-7), ctypes.c_longlong(-7)
+            rc = fn(*dims, ctypes.addressof(s), ctypes.addressof(c), ctypes.addressof(w))
+            got.append((rc, s.value, c.value, w.value))
+        return got
+
+    seen_ok = seen_split = seen_anyg_only = 0
+    for shape in _shapes():
+        for W in WINDOWS:
+            dims = shape + (W,)
+            pow2, anyg = plans(WINDOW_POW2, dims), plans(WINDOW_ANYG, dims)
+            assert len(set(pow2)) == 1, (dims, dict(zip(WINDOW_POW2, pow2)))
+            assert len(set(anyg)) == 1, (dims, dict(zip(WINDOW_ANYG, anyg)))
+            if pow2[0][0] == 0:  # what the power-of-two forms plan, the any-G forms plan alike
+                assert anyg[0] == pow2[0], (dims, pow2[0], anyg[0])
+                seen_ok += 1
+                seen_split += pow2[0][1] > 1
+            seen_anyg_only += anyg[0][0] == 0 and pow2[0][0] != 0
+    assert seen_ok and seen_split and seen_anyg_only  # (8, 3) is no integer group; (3, 1) and (16, 1) are groups only the any-G forms take
