@@ -401,6 +401,41 @@ def fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_plan(B, T, Hq, Hkv,
     return host.fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_plan(B, T, Hq, Hkv, max_pages, page, D, window)
 
 
+def kv_append_paged_varlen_d256_bf16(k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q=None, q_out=None, rope_table=None, rope="none"):
+    """kv_append_paged_varlen_bf16 at head dim 256 (Gemma-2, Gemma-3): bf16 rows and pools [P,Hkv,page,256], all three rope modes, the half-split
+    pairs (i, i + 128); any other head dim is refused. C entry cln_kv_append_paged_varlen_d256_bf16 (include/cln_amd_ext.h). Not a reference
+    name."""
+    from . import host
+    return host.kv_append_paged_varlen_d256_bf16(k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q, q_out, rope_table, rope)
+
+
+def fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, window, sinks, softmax_scale,
+                                                                softcap, out, lse=None):
+    """fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16 at head dim 256 (Gemma-2-2B / 9B: cap 50, window 4096; Gemma-3-1B / 4B / 12B): the
+    same arguments and semantics, D = 256 only. C entry cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16 (include/cln_amd_ext.h).
+    Not a reference name."""
+    from . import host
+    return host.fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, window, sinks,
+                                                                            softmax_scale, softcap, out, lse)
+
+
+def fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16(q, k_pages, v_pages, block_table, seqlens, window, sinks, softmax_scale, softcap,
+                                                              out, lse=None, workspace=None):
+    """fa2_decode_paged_multi_window_sink_softcap_anyg_bf16 at head dim 256: the same arguments and semantics, D = 256 only, T in 1 … 8 with
+    T * Hq / Hkv <= 32; the workspace is sized by fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_plan. C entry
+    cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16(q, k_pages, v_pages, block_table, seqlens, window, sinks, softmax_scale,
+                                                                          softcap, out, lse, workspace)
+
+
+def fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16: the entry's own plan (key step 64, D = 256);
+    window = None: no window. C entry cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_plan."""
+    from . import host
+    return host.fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

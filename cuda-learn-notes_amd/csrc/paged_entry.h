@@ -1,5 +1,5 @@
-// The host side of the paged KV-cache entries (cln_kv_append_paged*, cln_fa2_prefill_paged*, cln_fa2_decode_paged*): one
-// definition of every argument check, shape check, plan and compile-time dispatch that the 21 compile units share. Host code only -- the kernels
+// The host side of the paged KV-cache entries (cln_kv_append_paged*, cln_fa2_prefill_paged*, cln_fa2_decode_paged*; DESIGN 4.4.6, 4.4.8 - 4.4.10,
+// 4.4.16): one definition of every argument check, shape check, plan and compile-time dispatch that the 24 compile units share. Host code only -- the kernels
 // are siblings, one body per element type, for the measured reason given there; nothing here can change a kernel's schedule. A unit keeps its
 // entry points, its PagedKV / Args struct and its describe text.
 #pragma once
@@ -235,6 +235,58 @@ inline int softcap_describe(char* buf, int len, const char* kernel, int D, float
   if (n < len) n += snprintf(buf + n, len - n, "otherwise ");
   return n < len ? n : len - 1;
 }
+
+// ---------------------------------------------------------------- head dim 256 (the *_d256_* entries)
+// Siblings of append_shape, prefill_varlen_shape_anyg and multi_window_plan_anyg that take D = 256 and no other head dim: the same checks in the
+// same order with the same status codes, so an argument that is wrong for the sibling is wrong here in the same way. The functions above and
+// for_head_dim stay as they are: no existing entry takes 256.
+constexpr int kHeadDim256 = 256;
+template <class F>
+int for_head_dim_256(int D, F&& f) { return pick<kHeadDim256>(D, f); }
+inline int append_shape_d256(bool packed, int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int rope_mode, bool has_q, int* page_shift,
+                             long long* y) {
+  if (B <= 0 || T <= 0 || D <= 0 || Hq <= 0 || Hkv <= 0 || max_pages <= 0 || page <= 0 || Hq % Hkv != 0) return CLN_ERR_BAD_ARG;
+  if (D != kHeadDim256 || rope_mode < 0 || rope_mode > 2) return CLN_ERR_UNSUPPORTED;
+  fa2d::PagedGeometry g;
+  const int rc = fa2d::paged_geometry(1, 1, max_pages, page, &g);
+  if (rc != CLN_OK) return rc;
+  *page_shift = g.page_shift;
+  *y = kva::grid_y(packed ? 1 : B, T, Hq, Hkv, has_q, D, rope_mode);  // generic in D: 16 threads per row with the half-split pairs, else 32
+  return *y > 0 ? CLN_OK : CLN_ERR_UNSUPPORTED;
+}
+// the prefill keeps the 128-row tile: slots = total_q G / 128 + B
+inline int prefill_varlen_shape_anyg_d256(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D, fa2d::PagedGeometry* g,
+                                          long long* slots) {
+  if (B <= 0 || total_q <= 0 || D <= 0) return CLN_ERR_BAD_ARG;
+  const int rc = geometry_anyg(Hq, Hkv, max_pages, page, g);
+  if (rc != CLN_OK) return rc;
+  if (D != kHeadDim256) return CLN_ERR_UNSUPPORTED;
+  const long long R = (long long)total_q * g->group;
+  *slots = R / fa2pp::kRowTile + B;
+  if (R > 0x7fffffffLL || *slots > 0xffffffffLL / fa2d::kThreads / Hkv) return CLN_ERR_UNSUPPORTED;
+  return CLN_OK;
+}
+// The decode at D = 256 gives a wave one 16-key block per step, so its workgroup step is 64 keys and not fa2pm::kKeyStep: the unit and the span
+// are multi_window_unit / multi_window_span with that step. At most two row tiles: T <= 8 and T G <= 32, else -2.
+constexpr int kKeyStepD256 = 64, kMaxRowsD256 = 32;
+inline long long multi_window_unit_d256(int page) { return page > kKeyStepD256 ? page : kKeyStepD256; }
+inline long long multi_window_span_d256(int T, int page, int window, long long Nmax) {
+  const long long U = multi_window_unit_d256(page), reach = ((long long)window + T - 1 + U - 1) / U * U + U;
+  return reach < Nmax ? reach : Nmax;
+}
+inline int multi_window_plan_anyg_d256(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window, fa2d::PagedGeometry* g,
+                                       fa2d::Plan* p) {
+  if (B <= 0 || T <= 0 || D <= 0) return CLN_ERR_BAD_ARG;
+  int rc = geometry_anyg(Hq, Hkv, max_pages, page, g);
+  if (rc != CLN_OK) return rc;
+  if (D != kHeadDim256 || T > fa2pm::kMaxT || T * g->group > kMaxRowsD256) return CLN_ERR_UNSUPPORTED;
+  rc = window_arg(window);
+  if (rc != CLN_OK) return rc;
+  return fa2d::split_plan((long long)B * Hkv, (long long)B * T * Hq, multi_window_span_d256(T, page, window, g->Nmax),
+                          multi_window_unit_d256(page), D, p);
+}
+template <class F>
+int for_row_tiles_d256(int tiles, F&& f) { return pick<2, 1>(tiles, f); }
 
 // The arguments of a decode entry in the order of their status codes: the pointers (fa2d::check_pointers), P, the status of the entry's plan
 // and, where the plan splits the keys, the workspace. The *_sink_* entries put their fp32 sinks [Hq] last in `in`, behind seqlens.

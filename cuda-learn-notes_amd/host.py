@@ -741,15 +741,24 @@ _PAGED_GROUPS_ANYG, _PAGED_ROWS_ANYG = tuple(range(1, 17)), 64  # the *_anyg_* e
 _ROPE_MODES = {"none": 0, "half": 1, "interleaved": 2}
 
 
+_HEAD_DIMS = (64, 128)  # what every paged entry takes unless its wrapper says otherwise (the *_d256_* wrappers pass (256,): DESIGN 4.4.16)
+
+
+def _paged_headdim_error(name, D, head_dims):
+    if head_dims == _HEAD_DIMS:
+        return RuntimeError("%s: headdim %d not supported (64 or 128)" % (name, D))
+    return RuntimeError("%s: head dim %d not supported (%s)" % (name, D, " or ".join(map(str, head_dims))))
+
+
 def _paged_groups(name):
     """The group sizes Hq / Hkv the paged attention entry `name` takes."""
     return _PAGED_GROUPS_ANYG if "_anyg_" in name else _PAGED_GROUPS
 
 
-def _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D):
+def _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D, head_dims=_HEAD_DIMS):
     """The RuntimeError for status -2 of the paged decode entry `name`."""
-    if D not in (64, 128):
-        return RuntimeError("%s: headdim %d not supported (64 or 128)" % (name, D))
+    if D not in head_dims:
+        return _paged_headdim_error(name, D, head_dims)
     if Hkv > 0 and Hq % Hkv == 0 and Hq // Hkv not in _paged_groups(name):
         return RuntimeError("%s: group size %d (= Hq %d / Hkv %d) not supported (%s)"
                             % (name, Hq // Hkv, Hq, Hkv, "1 … 16" if "_anyg_" in name else "1, 2, 4 or 8"))
@@ -788,20 +797,22 @@ def _paged_sinks(sinks, q):
         raise RuntimeError("tensor must be contiguous (the kernels take raw data_ptr())")
 
 
-def _paged_plan(name, *dims, window=None):
+def _paged_plan(name, *dims, window=None, head_dims=_HEAD_DIMS, max_rows=_PAGED_ROWS_ANYG):
     """The body of the paged *_plan wrappers: the C entry cln_<name>_plan for dims = (B, Hq, Hkv, max_pages, page, D), or with a T behind B
-    for the multi-token entries, and its error texts; `window` goes behind D."""
+    for the multi-token entries, and its error texts; `window` goes behind D. head_dims and max_rows (the T * G an any-G entry takes at most)
+    are what the entry takes: they choose the text of a -2, never the status."""
     args = tuple(map(int, dims))
     rc, plan = _decode_plan("cln_%s_plan" % name, args + _paged_window(name, window))
     Hq, Hkv, max_pages, page, D = args[-5:]
     if rc == -2:
-        if len(args) == 7 and D in (64, 128) and args[1] > 8:
+        dims_ok = D in head_dims
+        if len(args) == 7 and dims_ok and args[1] > 8:
             raise RuntimeError("%s: T %d not supported (1 … 8)" % (name, args[1]))
-        if (len(args) == 7 and D in (64, 128) and "_anyg_" in name and Hkv > 0 and Hq % Hkv == 0 and Hq // Hkv in _PAGED_GROUPS_ANYG
-                and args[1] * (Hq // Hkv) > _PAGED_ROWS_ANYG):
+        if (len(args) == 7 and dims_ok and "_anyg_" in name and Hkv > 0 and Hq % Hkv == 0 and Hq // Hkv in _PAGED_GROUPS_ANYG
+                and args[1] * (Hq // Hkv) > max_rows):
             raise RuntimeError("%s: T %d x group size %d = %d query rows per KV head not supported (at most %d)"
-                               % (name, args[1], Hq // Hkv, args[1] * (Hq // Hkv), _PAGED_ROWS_ANYG))
-        raise _paged_unsupported(name, args[0], Hq, Hkv, max_pages, page, D)
+                               % (name, args[1], Hq // Hkv, args[1] * (Hq // Hkv), max_rows))
+        raise _paged_unsupported(name, args[0], Hq, Hkv, max_pages, page, D, head_dims)
     if rc == -1 and Hkv > 0 and Hq % Hkv:
         raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
     _raise(name, rc)
@@ -809,7 +820,7 @@ def _paged_plan(name, *dims, window=None):
 
 
 def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, out, lse, workspace,
-                     window=None, sinks=None, sinks_optional=False, floats=()):
+                     window=None, sinks=None, sinks_optional=False, floats=(), head_dims=_HEAD_DIMS):
     """The body of every attention entry over a paged cache. q, out: dtype [B,Hq,D] (q_dims = 3) or [B,T,Hq,D] (4), or with cu_q the packed
     [total_q,Hq,D]; the pools hold dtype, or with k_scale / v_scale e4m3; plan = the *_plan of a decode entry, which splits the keys and takes
     a workspace, or None for a prefill entry: one launch, and what cannot be launched is told here, in the words of the plan. window = the W of
@@ -852,8 +863,8 @@ def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table
         Hq = lead[-1]
         if Hq % Hkv:
             raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
-        if D not in (64, 128) or Hq // Hkv not in _paged_groups(name) or page not in _PAGED_PAGES:
-            raise _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D)
+        if D not in head_dims or Hq // Hkv not in _paged_groups(name) or page not in _PAGED_PAGES:
+            raise _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D, head_dims)
         ws = ()
         too_large = ("%s: max_pages * page or Hkv * (total_q * Hq / Hkv / 128 + B) too large for one launch" if packed else
                      "%s: max_pages * page or B * Hkv * ceil(T * Hq / Hkv / 128) too large for one launch") % name
@@ -865,7 +876,8 @@ def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table
     _raise(name, rc, too_large)
 
 
-def _kv_append_paged(name, dtype, k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, q, q_out, rope_table, rope):
+def _kv_append_paged(name, dtype, k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, q, q_out, rope_table, rope,
+                     head_dims=_HEAD_DIMS):
     """The body of every append entry. k_new, v_new: dtype [B,T,Hkv,D], or with cu_q the packed [total_q,Hkv,D]; q, q_out alike with Hq heads;
     the pools hold dtype, or with k_scale / v_scale e4m3."""
     packed, fp8 = cu_q is not None, k_scale is not None
@@ -911,8 +923,8 @@ def _kv_append_paged(name, dtype, k_new, v_new, k_pages, v_pages, block_table, s
             raise RuntimeError("Tensor size mismatch!")
         max_pos = rope_table.shape[0]
         _check_shape(rope_table, max_pos, D)
-    if D not in (64, 128):
-        raise RuntimeError("%s: headdim %d not supported (64 or 128)" % (name, D))
+    if D not in head_dims:
+        raise _paged_headdim_error(name, D, head_dims)
     if page not in _PAGED_PAGES:
         raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
     if Hq % Hkv:
@@ -1341,3 +1353,42 @@ def fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8(q, k_pages, v_pages
     _paged_attention(name, torch.bfloat16, 4, fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_plan, q, k_pages, v_pages, block_table,
                      seqlens, None, k_scale, v_scale, out, lse, workspace, _NO_WINDOW if window is None else window, sinks, True,
                      _paged_softcap(name, softmax_scale, softcap))
+
+
+def kv_append_paged_varlen_d256_bf16(k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, q=None, q_out=None, rope_table=None, rope="none"):
+    """kv_append_paged_varlen_bf16 at head dim 256: k_new, v_new torch.bfloat16 [total_q,Hkv,256], q, q_out [total_q,Hq,256], the
+    pools [P,Hkv,page,256], rope_table fp32 [max_pos,256]; rope "half" rotates the pairs (i, i + 128). Everything else -- liveness, the caller's
+    contract, the errors -- as there; any other head dim is refused. Deterministic. C entry cln_kv_append_paged_varlen_d256_bf16
+    (include/cln_amd_ext.h); no CPU path."""
+    _kv_append_paged("kv_append_paged_varlen_d256_bf16", torch.bfloat16, k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, None, None, q,
+                     q_out, rope_table, rope, head_dims=(256,))
+
+
+def fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16(q, k_pages, v_pages, block_table, seqlens, cu_q, window, sinks, softmax_scale,
+                                                                softcap, out, lse=None):
+    """fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16 at head dim 256: q, out torch.bfloat16 [total_q,Hq,256], the pools
+    [P,Hkv,page,256]; window, sinks, softmax_scale (None: 1 / 16) and softcap as there, each None-able; any other head dim is refused. C entry
+    cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16"
+    _paged_attention(name, torch.bfloat16, 3, None, q, k_pages, v_pages, block_table, seqlens, cu_q, None, None, out, lse, None,
+                     _NO_WINDOW if window is None else window, sinks, True, _paged_softcap(name, softmax_scale, softcap), head_dims=(256,))
+
+
+def fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16: the entry's own plan -- fa2d::split_plan on
+    the span of the window in units of max(page, 64), the 64-key step of its kernel, and D = 256; T in 1 … 8 with T * Hq / Hkv <= 32;
+    window = None: no window (2**31 - 1) (cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_plan, include/cln_amd_ext.h). No GPU
+    needed."""
+    return _paged_plan("fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16", B, T, Hq, Hkv, max_pages, page, D,
+                       window=_NO_WINDOW if window is None else window, head_dims=(256,), max_rows=32)
+
+
+def fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16(q, k_pages, v_pages, block_table, seqlens, window, sinks, softmax_scale, softcap,
+                                                              out, lse=None, workspace=None):
+    """fa2_decode_paged_multi_window_sink_softcap_anyg_bf16 at head dim 256: q, out torch.bfloat16 [B,T,Hq,256], T in 1 … 8 with
+    T * Hq / Hkv <= 32; fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_plan(...)[2] workspace bytes; everything else as there. C entry
+    cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16"
+    _paged_attention(name, torch.bfloat16, 4, fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_plan, q, k_pages, v_pages, block_table,
+                     seqlens, None, None, None, out, lse, workspace, _NO_WINDOW if window is None else window, sinks, True,
+                     _paged_softcap(name, softmax_scale, softcap), head_dims=(256,))

@@ -701,6 +701,32 @@ def describe_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8(B, T, Hq, Hkv,
                              softmax_scale, softcap)
 
 
+def describe_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16(B, total_q, Hq, Hkv, max_pages, page, D, window, softmax_scale=None,
+                                                                     softcap=None):
+    """describe() for cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16 (include/cln_amd_ext.h): the kernel
+    instantiation <D=256,CAP=...>, the scale and cap, the tile, the key step and the LDS bytes (no GPU needed). ValueError for an unsupported or
+    invalid shape (any D but 256), window, scale or cap."""
+    return _describe_softcap("cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16", (B, total_q, Hq, Hkv, max_pages, page, D, window),
+                             softmax_scale, softcap)
+
+
+def describe_decode_paged_multi_window_sink_softcap_anyg_d256_bf16(B, T, Hq, Hkv, max_pages, page, D, window, softmax_scale=None, softcap=None):
+    """describe() for cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16 (include/cln_amd_ext.h): the kernel
+    instantiation <D=256,MT=...,CAP=...>, the key step, the LDS bytes and the entry's own split plan (no GPU needed). ValueError for an unsupported
+    or invalid shape (any D but 256, T G > 32), window, scale or cap."""
+    return _describe_softcap("cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16", (B, T, Hq, Hkv, max_pages, page, D, window),
+                             softmax_scale, softcap)
+
+
+def describe_kv_append_paged_varlen_d256_bf16(B, total_q, Hq, Hkv, max_pages, page, D, rope_mode):
+    """describe() for cln_kv_append_paged_varlen_d256_bf16 (include/cln_amd_ext.h): the kernel instantiation and the launch as text
+    (no GPU needed). rope_mode: 0 / "none", 1 / "half", 2 / "interleaved". ValueError for an unsupported or invalid shape (any D but 256)."""
+    mode = {"none": 0, "half": 1, "interleaved": 2}.get(rope_mode, rope_mode)
+    if not isinstance(mode, int):
+        raise ValueError("cln_kv_append_paged_varlen_d256_bf16: rope %r not supported" % (rope_mode,))
+    return _describe_bf16("cln_kv_append_paged_varlen_d256_bf16", tuple(int(x) for x in (B, total_q, Hq, Hkv, max_pages, page, D)) + (mode,))
+
+
 def describe_kv_append_paged_varlen_bf16_fp8(B, total_q, Hq, Hkv, max_pages, page, D, rope_mode):
     """describe() for cln_kv_append_paged_varlen_bf16_fp8 (include/cln_amd_ext.h): the kernel instantiation and the launch as text (no GPU
     needed). rope_mode: 0 / "none", 1 / "half", 2 / "interleaved". ValueError for an unsupported or invalid shape."""

@@ -493,6 +493,44 @@ int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8(const void* q, 
 int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D,
                                                                           int window, float softmax_scale, float softcap, char* buf, int len);
 
+/* ---- HEAD DIM 256 on the bf16 paged path: the entries above take D = 64 and 128 and keep refusing every other head
+ * dim with -2; these seven are siblings that take D = 256 and nothing else (-2 for 64, 128, 96 ...). Gemma-2 (2B, 9B: cap 50, W 4096) and
+ * Gemma-3 (1B, 4B, 12B: W 512 / 1024) have D = 256.
+ *
+ * cln_kv_append_paged_varlen_d256_bf16: cln_kv_append_paged_varlen_bf16 on pools bf16 [P,Hkv,page,256]; all three rope modes, the half-split
+ * pairs are (i, i + 128). Arguments, checks and status codes are that entry's, in its order.
+ * cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16: cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_bf16 at D = 256, the
+ * same semantics: cap before the mask, the sink neither scaled nor capped, a row that sees no key O = 0 and LSE = -inf, no page and no table
+ * entry wholly below the window read. Arguments, checks and status codes are that entry's, in its order (the two floats first).
+ * cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16: cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16 at D = 256 for T in
+ * 1 ... 8, G in 1 ... 16 and T G <= 32 (more: -2). Its _plan is its own -- the kernel's key step is 64, not 128, so the chunk is a multiple of
+ * max(page, 64) -- and the workspace is sized from it: rows S (256 + 2) 4 bytes when S > 1. Arguments, checks and status codes are that
+ * entry's, in its order.
+ * Scores and accumulators fp32, both products on v_mfma_f32_16x16x32_bf16, P and O rounded once to bf16; nothing passes through fp16.
+ */
+int cln_kv_append_paged_varlen_d256_bf16(const void* k_new, const void* v_new, void* k_pages, void* v_pages, const int* block_table,
+                                         const int* seqlens, const int* cu_q, const void* q, void* q_out, const float* rope_table, int B,
+                                         int total_q, int Hq, int Hkv, int P, int max_pages, int page, int D, int max_pos, int rope_mode,
+                                         void* stream);
+int cln_kv_append_paged_varlen_d256_bf16_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D, int rope_mode, char* buf,
+                                                  int len);
+int cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16(const void* q, const void* k_pages, const void* v_pages,
+                                                                    const int* block_table, const int* seqlens, const int* cu_q,
+                                                                    const float* sinks /* may be NULL */, void* o, float* lse, int B, int total_q,
+                                                                    int Hq, int Hkv, int P, int max_pages, int page, int D, int window,
+                                                                    float softmax_scale, float softcap, void* stream);
+int cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page, int D,
+                                                                             int window, float softmax_scale, float softcap, char* buf, int len);
+int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window,
+                                                                       int* splits, int* chunk, long long* workspace_bytes);
+int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16(const void* q, const void* k_pages, const void* v_pages, const int* block_table,
+                                                                  const int* seqlens, const float* sinks /* may be NULL */, void* o, float* lse,
+                                                                  void* workspace, long long workspace_bytes, int B, int T, int Hq, int Hkv, int P,
+                                                                  int max_pages, int page, int D, int window, float softmax_scale, float softcap,
+                                                                  void* stream);
+int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D,
+                                                                           int window, float softmax_scale, float softcap, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
