@@ -436,6 +436,31 @@ def fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_plan(B, T, Hq, Hkv
     return host.fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_plan(B, T, Hq, Hkv, max_pages, page, D, window)
 
 
+def fa2_decode_paged_mla_bf16(q, pool, block_table, seqlens, softmax_scale, out, lse=None, workspace=None):
+    """Multi-head latent attention (DeepSeek-V2 / V3 / R1, Kimi-K2) decode over a paged latent cache: q bf16 [B,T,Hq,576], already absorbed
+    (q_nope W_UK | q_pe); pool bf16 [P,page,576] of rows [c 512 | k_pe 64], each the key (576 dims) and the value (dims 0 … 511) of every head;
+    out bf16 [B,T,Hq,512] in latent space; lse fp32 [B,T,Hq] or None. softmax_scale is required (finite, > 0). T in 1 … 8, Hq in 1 … 128; the
+    workspace is sized by fa2_decode_paged_mla_bf16_plan. C entry cln_fa2_decode_paged_mla_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_decode_paged_mla_bf16(q, pool, block_table, seqlens, softmax_scale, out, lse, workspace)
+
+
+def fa2_decode_paged_mla_bf16_plan(B, T, Hq, max_pages, page):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_bf16: a function of these five numbers only (row groups of 64 query rows, key
+    step 64, D = 512). C entry cln_fa2_decode_paged_mla_bf16_plan."""
+    from . import host
+    return host.fa2_decode_paged_mla_bf16_plan(B, T, Hq, max_pages, page)
+
+
+def kv_append_paged_mla_bf16(c_new, k_pe_new, pool, block_table, seqlens, cu_q, q=None, q_out=None, rope_table=None, rope="none"):
+    """Append a packed batch of latent rows to the paged latent cache of fa2_decode_paged_mla_bf16: c_new bf16 [total_q,512] copied bit for bit,
+    k_pe_new bf16 [total_q,64] rotated at the token's position; q / q_out bf16 [total_q,Hq,576] alike (dims 0 … 511 copied, 512 … 575 rotated);
+    rope_table fp32 [max_pos,64] (kv_append_rope_table(max_pos, 64)); rope "none", "half" (pairs (i, i + 32)) or "interleaved". C entry
+    cln_kv_append_paged_mla_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.kv_append_paged_mla_bf16(c_new, k_pe_new, pool, block_table, seqlens, cu_q, q, q_out, rope_table, rope)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

@@ -288,6 +288,44 @@ inline int multi_window_plan_anyg_d256(int B, int T, int Hq, int Hkv, int max_pa
 template <class F>
 int for_row_tiles_d256(int tiles, F&& f) { return pick<2, 1>(tiles, f); }
 
+// ---------------------------------------------------------------- multi-head latent attention (the *_mla_* entries)
+// One pool of latent rows [P, page, 576] = [c (512) | k_pe (64)], shared by every query head: Hkv = 1 by construction, the key has 576 dims and
+// the value the first 512 of them. Nothing above changes: no existing entry takes these shapes.
+constexpr int kMlaDc = 512, kMlaDr = 64, kMlaDk = kMlaDc + kMlaDr, kMlaMaxHq = 128, kMlaRowGroup = 64, kMlaKeyStep = 64;
+// The softmax scale of the decode entry has no default (the models use 192^-1/2 mscale^2, not 576^-1/2): finite and > 0, else -1 (a NaN
+// fails the comparison). *mult = x log2(e), formed in double and rounded once, as softcap_arg forms it for a scale of the caller's.
+inline int mla_scale_arg(float softmax_scale, float* mult) {
+  if (!(softmax_scale > 0.0f) || std::isinf(softmax_scale)) return CLN_ERR_BAD_ARG;
+  constexpr double kLog2e = 1.4426950408889634, kMax = 3.4028234663852886e38;
+  const double x = (double)softmax_scale * kLog2e;
+  *mult = (float)(x < kMax ? x : kMax);
+  return CLN_OK;
+}
+// The split plan of the decode: a workgroup serves one (sequence, split, row group of 64 of the R = T Hq query rows), so
+// fa2d::split_plan(bk = B ceil(R / 64), rows = B R, Nmax, unit = max(page, 64), D = 512): a function of the shape only. -1 for a non-positive
+// dimension, -2 for T > 8, Hq > 128, another page, max_pages page >= 2^31 or a grid that does not fit.
+inline int mla_plan(int B, int T, int Hq, int max_pages, int page, fa2d::PagedGeometry* g, fa2d::Plan* p) {
+  if (B <= 0 || T <= 0 || Hq <= 0) return CLN_ERR_BAD_ARG;
+  const int rc = fa2d::paged_geometry(1, 1, max_pages, page, g);
+  if (rc != CLN_OK) return rc;
+  if (T > fa2pm::kMaxT || Hq > kMlaMaxHq) return CLN_ERR_UNSUPPORTED;
+  const long long R = (long long)T * Hq, row_groups = (R + kMlaRowGroup - 1) / kMlaRowGroup;
+  return fa2d::split_plan(B * row_groups, B * R, g->Nmax, page > kMlaKeyStep ? page : kMlaKeyStep, kMlaDc, p);
+}
+// The append: a thread per 16-byte piece; per token one pool row and, with q, Hq query rows of 64 copied pieces and the rotary pieces (4 with
+// the half-split pairs, which a thread moves two at a time, else 8). *y = the workgroups per token.
+inline int mla_append_pieces(int rope_mode) { return kMlaDc / 8 + (rope_mode == 1 ? kMlaDr / 16 : kMlaDr / 8); }
+inline int mla_append_shape(int B, int total_q, int Hq, int max_pages, int page, int rope_mode, bool has_q, int* page_shift, long long* y) {
+  if (B <= 0 || total_q <= 0 || Hq <= 0 || max_pages <= 0 || page <= 0) return CLN_ERR_BAD_ARG;
+  if (rope_mode < 0 || rope_mode > 2) return CLN_ERR_UNSUPPORTED;
+  fa2d::PagedGeometry g;
+  const int rc = fa2d::paged_geometry(1, 1, max_pages, page, &g);
+  if (rc != CLN_OK) return rc;
+  *page_shift = g.page_shift;
+  *y = ((1LL + (has_q ? Hq : 0)) * mla_append_pieces(rope_mode) + kva::kThreads - 1) / kva::kThreads;
+  return *y <= 65535 ? CLN_OK : CLN_ERR_UNSUPPORTED;
+}
+
 // The arguments of a decode entry in the order of their status codes: the pointers (fa2d::check_pointers), P, the status of the entry's plan
 // and, where the plan splits the keys, the workspace. The *_sink_* entries put their fp32 sinks [Hq] last in `in`, behind seqlens.
 inline int decode_args(const void* const* in, int n_in, const void* const (&out)[3], long long workspace_bytes, int P, int plan_rc,

@@ -1392,3 +1392,115 @@ def fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16(q, k_pages, v_page
     _paged_attention(name, torch.bfloat16, 4, fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_plan, q, k_pages, v_pages, block_table,
                      seqlens, None, None, None, out, lse, workspace, _NO_WINDOW if window is None else window, sinks, True,
                      _paged_softcap(name, softmax_scale, softcap), head_dims=(256,))
+
+
+# ---- multi-head latent attention over a paged latent cache: one pool bf16 [P,page,576] of rows [c 512 | k_pe 64]
+_MLA_DC, _MLA_DR, _MLA_DK, _MLA_MAX_HQ = 512, 64, 576, 128
+
+
+def fa2_decode_paged_mla_bf16_plan(B, T, Hq, max_pages, page):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_bf16: fa2d::split_plan on B * ceil(T * Hq / 64) workgroup jobs (a row group of
+    64 query rows each), in units of max(page, 64) keys, at D = 512; a function of these five numbers only (cln_fa2_decode_paged_mla_bf16_plan,
+    include/cln_amd_ext.h). T in 1 … 8, Hq in 1 … 128. No GPU needed."""
+    name = "fa2_decode_paged_mla_bf16"
+    B, T, Hq, max_pages, page = (int(x) for x in (B, T, Hq, max_pages, page))
+    rc, plan = _decode_plan("cln_%s_plan" % name, (B, T, Hq, max_pages, page))
+    if rc == -2:
+        if T > 8:
+            raise RuntimeError("%s: T %d not supported (1 … 8)" % (name, T))
+        if Hq > _MLA_MAX_HQ:
+            raise RuntimeError("%s: %d query heads not supported (1 … %d)" % (name, Hq, _MLA_MAX_HQ))
+        if page not in _PAGED_PAGES:
+            raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+        raise RuntimeError("%s: max_pages * page or B * ceil(T * Hq / 64) * splits too large for one launch" % name)
+    _raise(name, rc)
+    return plan
+
+
+def fa2_decode_paged_mla_bf16(q, pool, block_table, seqlens, softmax_scale, out, lse=None, workspace=None):
+    """Multi-head latent attention decode over a paged latent cache into out: q torch.bfloat16 [B,T,Hq,576], already absorbed by the model
+    (q_nope W_UK in dims 0 … 511, q_pe in 512 … 575); pool torch.bfloat16 [P,page,576], a row [c 512 | k_pe 64] stored once and shared by all
+    query heads: the key is the whole row, the value its dims 0 … 511; block_table int32 [B,max_pages] and seqlens int32 [B] on the GPU (never
+    read by the host; lengths clamped to [0, max_pages * page] by the kernels; the live table entries must lie in [0, P)); out torch.bfloat16
+    [B,T,Hq,512] in latent space; lse fp32 [B,T,Hq] (natural log) or None. seqlens[b] counts the T newest tokens; query t sees the keys
+    j < len_b - (T - 1 - t), and a query that sees none gets O = 0 and LSE = -inf. softmax_scale: required, finite and > 0 (the models use
+    192 ** -0.5 * mscale ** 2, not 576 ** -0.5). T in 1 … 8, Hq in 1 … 128, page in {16, 32, 64, 128, 256}. workspace: any contiguous GPU tensor
+    of at least fa2_decode_paged_mla_bf16_plan(...)[2] bytes; allocated here on the current stream when None and the plan splits the keys.
+    Deterministic. C entry cln_fa2_decode_paged_mla_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "fa2_decode_paged_mla_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 7 + [ctypes.c_longlong] + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_void_p])
+    scale = float(softmax_scale)
+    if not (0.0 < scale < math.inf):
+        raise RuntimeError("%s: softmax_scale %r not supported (finite and > 0; there is no default)" % (name, softmax_scale))
+    _decode_check((q, pool, out), (block_table, seqlens), torch.bfloat16)
+    if q.dim() != 4 or pool.dim() != 3 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    B, T, Hq, Dk = q.shape
+    P, page, _ = pool.shape
+    if Dk != _MLA_DK:
+        raise RuntimeError("%s: q of %d dims not supported (%d = 512 latent + 64 rotary)" % (name, Dk, _MLA_DK))
+    _check_shape(pool, P, page, _MLA_DK)
+    if block_table.shape[0] != B:
+        raise RuntimeError("Tensor size mismatch!")
+    max_pages = block_table.shape[1]
+    _check_shape(out, B, T, Hq, _MLA_DC)
+    _check_shape(seqlens, B)
+    lse_ptr = _decode_lse(lse, B, T, Hq)
+    ws_ptr, ws_bytes = _decode_workspace(name, fa2_decode_paged_mla_bf16_plan(B, T, Hq, max_pages, page)[2], workspace, q.device)
+    rc = fn(q.data_ptr(), pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), out.data_ptr(), lse_ptr, ws_ptr, ws_bytes, B, T, Hq, P,
+            max_pages, page, scale, _stream())
+    _raise(name, rc)
+
+
+def kv_append_paged_mla_bf16(c_new, k_pe_new, pool, block_table, seqlens, cu_q, q=None, q_out=None, rope_table=None, rope="none"):
+    """Write the latent rows of a packed batch of new tokens into the paged latent cache of fa2_decode_paged_mla_bf16, with the rotary embedding
+    of k_pe and q_pe fused in; one launch. c_new torch.bfloat16 [total_q,512] goes to pool dims 0 … 511 bit for bit, k_pe_new torch.bfloat16
+    [total_q,64] to dims 512 … 575, rotated; pool torch.bfloat16 [P,page,576], written in place; q, q_out torch.bfloat16 [total_q,Hq,576], given
+    together or both None (q_out may be q): dims 0 … 511 copied bit for bit, dims 512 … 575 rotated at the same position. cu_q int32 [B+1],
+    block_table int32 [B,max_pages], seqlens int32 [B] on the GPU (never read by the host), as for kv_append_paged_varlen_bf16: token i of
+    sequence b is packed row cu_q[b] + i and stands at pos = seqlens[b] - T_b + i; liveness and the caller's contract as there; packed rows
+    outside [cu_q[0], cu_q[B]) are neither read nor written. rope: "none" (the rotary dims are copied; no rope_table), "half" (pairs
+    (i, i + 32)) or "interleaved" (pairs (2i, 2i + 1)), rotated in fp32 by rope_table fp32 [max_pos,64] (kv_append_rope_table(max_pos, 64)) with
+    one rounding. Deterministic. C entry cln_kv_append_paged_mla_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "kv_append_paged_mla_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 9 + [ctypes.c_int] * 8 + [ctypes.c_void_p])
+    if rope not in _ROPE_MODES:
+        raise RuntimeError("%s: rope %r not supported ('none', 'half' or 'interleaved')" % (name, rope))
+    mode = _ROPE_MODES[rope]
+    if mode == 0 and rope_table is not None:
+        raise RuntimeError("%s: rope 'none' takes no rope_table" % name)
+    if mode != 0 and rope_table is None:
+        raise RuntimeError("%s: rope %r needs a rope_table (kv_append_rope_table(max_pos, 64))" % (name, rope))
+    if (q is None) != (q_out is None):
+        raise RuntimeError("%s: q and q_out are given together or not at all" % name)
+    _decode_check((c_new, k_pe_new, pool) + ((q, q_out) if q is not None else ()), (block_table, seqlens, cu_q), torch.bfloat16)
+    if c_new.dim() != 2 or k_pe_new.dim() != 2 or pool.dim() != 3 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    total_q = c_new.shape[0]
+    P, page, _ = pool.shape
+    B, max_pages = block_table.shape
+    _check_shape(c_new, total_q, _MLA_DC)
+    _check_shape(k_pe_new, total_q, _MLA_DR)
+    _check_shape(pool, P, page, _MLA_DK)
+    _check_shape(seqlens, B)
+    _check_shape(cu_q, B + 1)
+    Hq, max_pos = 1, 0
+    if q is not None:
+        if q.dim() != 3:
+            raise RuntimeError("Tensor size mismatch!")
+        Hq = q.shape[1]
+        _check_shape(q, total_q, Hq, _MLA_DK)
+        _check_shape(q_out, total_q, Hq, _MLA_DK)
+    if rope_table is not None:
+        _check_dtype(rope_table, torch.float32)
+        _check_dev(rope_table)
+        if rope_table.dim() != 2:
+            raise RuntimeError("Tensor size mismatch!")
+        max_pos = rope_table.shape[0]
+        _check_shape(rope_table, max_pos, _MLA_DR)
+    if page not in _PAGED_PAGES:
+        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    rc = fn(c_new.data_ptr(), k_pe_new.data_ptr(), pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), cu_q.data_ptr(), ptr(q), ptr(q_out),
+            ptr(rope_table), B, total_q, Hq, P, max_pages, page, max_pos, mode, _stream())
+    _raise(name, rc, "%s: max_pages * page or total_q too large for one launch" % name)

@@ -727,6 +727,22 @@ def describe_kv_append_paged_varlen_d256_bf16(B, total_q, Hq, Hkv, max_pages, pa
     return _describe_bf16("cln_kv_append_paged_varlen_d256_bf16", tuple(int(x) for x in (B, total_q, Hq, Hkv, max_pages, page, D)) + (mode,))
 
 
+def describe_decode_paged_mla_bf16(B, T, Hq, max_pages, page, softmax_scale):
+    """describe() for cln_fa2_decode_paged_mla_bf16 (include/cln_amd_ext.h): the kernel, the scale in use, the row groups, the
+    split plan, the LDS image and the MFMAs per step as text (no GPU needed). ValueError for an unsupported or invalid shape or scale (the
+    scale is required: finite and > 0)."""
+    return _describe_bf16("cln_fa2_decode_paged_mla_bf16", tuple(int(x) for x in (B, T, Hq, max_pages, page)), 2048, (float(softmax_scale),))
+
+
+def describe_kv_append_paged_mla_bf16(B, total_q, Hq, max_pages, page, rope_mode):
+    """describe() for cln_kv_append_paged_mla_bf16 (include/cln_amd_ext.h): the kernel instantiation and the launch as text (no
+    GPU needed). rope_mode: 0 / "none", 1 / "half", 2 / "interleaved". ValueError for an unsupported or invalid shape."""
+    mode = {"none": 0, "half": 1, "interleaved": 2}.get(rope_mode, rope_mode)
+    if not isinstance(mode, int):
+        raise ValueError("cln_kv_append_paged_mla_bf16: rope %r not supported" % (rope_mode,))
+    return _describe_bf16("cln_kv_append_paged_mla_bf16", tuple(int(x) for x in (B, total_q, Hq, max_pages, page)) + (mode,))
+
+
 def describe_kv_append_paged_varlen_bf16_fp8(B, total_q, Hq, Hkv, max_pages, page, D, rope_mode):
     """describe() for cln_kv_append_paged_varlen_bf16_fp8 (include/cln_amd_ext.h): the kernel instantiation and the launch as text (no GPU
     needed). rope_mode: 0 / "none", 1 / "half", 2 / "interleaved". ValueError for an unsupported or invalid shape."""

@@ -531,6 +531,35 @@ int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16(const void* q,
 int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D,
                                                                            int window, float softmax_scale, float softcap, char* buf, int len);
 
+/* ---- MULTI-HEAD LATENT ATTENTION (MLA) over a paged latent cache, bf16: the cache of DeepSeek-V2 / V3 / R1 and
+ * Kimi-K2. One pool bf16 [P, page, 576] of latent rows [c (512) | k_pe (64)], stored once and shared by every query head: the same row is the
+ * key (all 576 dims) and the value (dims 0 ... 511); Hkv = 1 by construction. page a power of two in 16 ... 256, block_table int32
+ * [B, max_pages], seqlens int32 [B] on the device, counting the new tokens, max_pages page < 2^31.
+ *
+ * cln_fa2_decode_paged_mla_bf16: q bf16 [B,T,Hq,576], already absorbed by the model (q_nope W_UK in dims 0 ... 511, q_pe in 512 ... 575); o bf16
+ * [B,T,Hq,512] in latent space (the model applies W_UV); lse fp32 [B,T,Hq], natural log, or NULL. Query (b, t, h) sees the keys
+ * j < len_b - (T - 1 - t); s_j = softmax_scale q . row_j[0:576]; O = softmax(s) row[:, 0:512], rounded once; a row that sees no key gets O = 0 and
+ * LSE = -inf. softmax_scale is required, finite and > 0 (the models use 192^-1/2 mscale^2): anything else is -1, checked first. T in 1 ... 8, Hq in
+ * 1 ... 128 (more: -2), any R = T Hq; rows are ordered r = t Hq + h. No window, no sinks, no cap. The workspace is that of _plan,
+ * B T Hq S (512 + 2) 4 bytes when S > 1; the plan is a function of the shape only: fa2d::split_plan on B ceil(T Hq / 64) workgroup jobs in units of
+ * max(page, 64) keys. Statuses as the siblings': -1 for a bad argument, -2 for unsupported. Every pool row is fetched from global memory once per
+ * workgroup and serves both products, on v_mfma_f32_16x16x32_bf16 with fp32 scores and accumulators; nothing passes through fp16.
+ * cln_kv_append_paged_mla_bf16: a packed batch in the cu_q convention of cln_kv_append_paged_varlen_bf16. c_new bf16 [total_q,512] goes to pool
+ * dims 0 ... 511 bit for bit, k_pe_new bf16 [total_q,64] to dims 512 ... 575, rotated at the token's position seqlens[b] - T_b + i; q / q_out bf16
+ * [total_q,Hq,576] or both NULL (q_out may be q): dims 0 ... 511 copied bit for bit, dims 512 ... 575 rotated at the same position. rope_table fp32
+ * [max_pos,64] = [cos 32 | sin 32]; rope_mode 0 none (no table; the rotary dims are copied), 1 half-split pairs (i, i + 32), 2 interleaved. The
+ * rotation is the bf16 append's: fp32 from the bf16 inputs, one rounding. One launch, nothing read on the host, rows of no sequence untouched.
+ */
+int cln_fa2_decode_paged_mla_bf16_plan(int B, int T, int Hq, int max_pages, int page, int* splits, int* chunk, long long* workspace_bytes);
+int cln_fa2_decode_paged_mla_bf16(const void* q, const void* pool, const int* block_table, const int* seqlens, void* o, float* lse,
+                                  void* workspace, long long workspace_bytes, int B, int T, int Hq, int P, int max_pages, int page,
+                                  float softmax_scale, void* stream);
+int cln_fa2_decode_paged_mla_bf16_describe(int B, int T, int Hq, int max_pages, int page, float softmax_scale, char* buf, int len);
+int cln_kv_append_paged_mla_bf16(const void* c_new, const void* k_pe_new, void* pool, const int* block_table, const int* seqlens,
+                                 const int* cu_q, const void* q, void* q_out, const float* rope_table, int B, int total_q, int Hq, int P,
+                                 int max_pages, int page, int max_pos, int rope_mode, void* stream);
+int cln_kv_append_paged_mla_bf16_describe(int B, int total_q, int Hq, int max_pages, int page, int rope_mode, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
