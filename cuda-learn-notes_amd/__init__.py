@@ -461,6 +461,33 @@ def kv_append_paged_mla_bf16(c_new, k_pe_new, pool, block_table, seqlens, cu_q, 
     return host.kv_append_paged_mla_bf16(c_new, k_pe_new, pool, block_table, seqlens, cu_q, q, q_out, rope_table, rope)
 
 
+def fa2_prefill_varlen_mla_bf16(q, kv, k_pe, cu_q, cu_k, softmax_scale, out, lse=None, causal=True):
+    """Multi-head latent attention prefill (un-absorbed: key 192 = 128 nope + 64 rotary dims, value 128, Hkv = Hq) of a packed batch: q bf16
+    [total_q,Hq,192], kv bf16 [total_k,Hq,256] = [k_nope | v] as kv_b_proj writes it, k_pe bf16 [total_k,64] shared by every head, cu_q / cu_k
+    int32 [B+1] on the GPU, out bf16 [total_q,Hq,128], lse fp32 [total_q,Hq] or None. causal=True: query t sees the keys j < L_b - (T_b - 1 - t);
+    False: all L_b (a context chunk). softmax_scale is required (finite, > 0). Hq in 1 … 128. C entry cln_fa2_prefill_varlen_mla_bf16
+    (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_prefill_varlen_mla_bf16(q, kv, k_pe, cu_q, cu_k, softmax_scale, out, lse, causal)
+
+
+def attn_merge_states_bf16(o_a, lse_a, o_b, lse_b, out, lse=None):
+    """Merge two attention states over disjoint key sets (chunked prefill): o_a, o_b bf16 [..., D], lse_a, lse_b fp32 [...], out bf16 (may be
+    o_a), lse fp32 or None (may be lse_a); D % 8 == 0, 8 <= D <= 512. A side whose LSE is -inf is selected out; both -inf give O = 0, LSE =
+    -inf. C entry cln_attn_merge_states_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.attn_merge_states_bf16(o_a, lse_a, o_b, lse_b, out, lse)
+
+
+def kv_gather_paged_mla_bf16(pool, block_table, cu_k, out, starts=None):
+    """Gather latent rows out of the paged latent cache into a packed batch, the mirror of kv_append_paged_mla_bf16: pool bf16 [P,page,576],
+    block_table int32 [B,max_pages], cu_k int32 [B+1], starts int32 [B] or None (0), out bf16 [total_k,576]; packed row cu_k[b] + i = cache row
+    starts[b] + i, bit for bit; rows at or past max_pages * page are zeros. C entry cln_kv_gather_paged_mla_bf16 (include/cln_amd_ext.h). Not a
+    reference name."""
+    from . import host
+    return host.kv_gather_paged_mla_bf16(pool, block_table, cu_k, out, starts)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

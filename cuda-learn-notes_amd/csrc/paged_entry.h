@@ -326,6 +326,44 @@ inline int mla_append_shape(int B, int total_q, int Hq, int max_pages, int page,
   return *y <= 65535 ? CLN_OK : CLN_ERR_UNSUPPORTED;
 }
 
+// ---------------------------------------------------------------- MLA prefill, state merge and gather
+// The un-absorbed prompt path: per head a key of 192 dims [k_nope 128 | k_pe 64] and a value of 128, Hkv = Hq, nothing paged. Nothing above
+// changes.
+constexpr int kMlaDn = 128, kMlaDq = kMlaDn + kMlaDr, kMlaDv = 128;
+// The prefill's pointers: q, kv, k_pe 16-byte aligned, cu_q and cu_k 4-byte, all required; o 16-byte aligned; lse may be null, 4-byte aligned;
+// no output is an input or the other output.
+inline int mla_prefill_args(const void* q, const void* kv, const void* k_pe, const int* cu_q, const int* cu_k, const void* o, const float* lse) {
+  const void* const in[] = {q, kv, k_pe, cu_q, cu_k};
+  for (int i = 0; i < 5; ++i)
+    if (!in[i] || !cln_aligned(in[i], i >= 3 ? 4 : 16)) return CLN_ERR_BAD_ARG;
+  if (!o || !cln_aligned16(o) || !cln_aligned(lse, 4) || (const void*)lse == o) return CLN_ERR_BAD_ARG;
+  for (int i = 0; i < 5; ++i)
+    if (o == in[i] || (lse && (const void*)lse == in[i])) return CLN_ERR_BAD_ARG;
+  return CLN_OK;
+}
+// -1 for a non-positive dimension, -2 for Hq > 128, a causal flag that is neither 0 nor 1, or a grid that does not fit. *slots = the workgroups
+// per head, total_q / 128 + B (prefill_varlen_shape at G = 1): the offsets stay on the device.
+inline int mla_prefill_shape(int B, int total_q, int total_k, int Hq, int causal, long long* slots) {
+  if (B <= 0 || total_q <= 0 || total_k <= 0 || Hq <= 0) return CLN_ERR_BAD_ARG;
+  if (Hq > kMlaMaxHq || (causal != 0 && causal != 1)) return CLN_ERR_UNSUPPORTED;
+  *slots = (long long)total_q / fa2pp::kRowTile + B;
+  return *slots > 0xffffffffLL / fa2d::kThreads / Hq ? CLN_ERR_UNSUPPORTED : CLN_OK;
+}
+// The merge of two attention states: a workgroup of 256 threads serves 256 / (D / 8) whole rows, a thread per 16-byte piece. -1 for a
+// non-positive dimension, -2 for a D outside 8 ... 512 or no multiple of 8, or a grid that does not fit. *rows_per_wg, *wgs: the launch.
+constexpr int kMergeThreads = 256, kMergeMaxD = 512;
+inline int merge_shape(long long rows, int D, int* rows_per_wg, long long* wgs) {
+  if (rows <= 0 || D <= 0) return CLN_ERR_BAD_ARG;
+  if (D % 8 != 0 || D > kMergeMaxD) return CLN_ERR_UNSUPPORTED;
+  *rows_per_wg = kMergeThreads / (D / 8);
+  *wgs = (rows + *rows_per_wg - 1) / *rows_per_wg;
+  return *wgs > 0x7fffffffLL ? CLN_ERR_UNSUPPORTED : CLN_OK;
+}
+// The gather out of the latent pool: the append's launch shape without q, a packed row x the 72 pieces of its latent row.
+inline int mla_gather_shape(int B, int total_k, int max_pages, int page, int* page_shift, long long* y) {
+  return mla_append_shape(B, total_k, 1, max_pages, page, 0, false, page_shift, y);
+}
+
 // The arguments of a decode entry in the order of their status codes: the pointers (fa2d::check_pointers), P, the status of the entry's plan
 // and, where the plan splits the keys, the workspace. The *_sink_* entries put their fp32 sinks [Hq] last in `in`, behind seqlens.
 inline int decode_args(const void* const* in, int n_in, const void* const (&out)[3], long long workspace_bytes, int P, int plan_rc,

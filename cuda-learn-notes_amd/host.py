@@ -1504,3 +1504,102 @@ def kv_append_paged_mla_bf16(c_new, k_pe_new, pool, block_table, seqlens, cu_q, 
     rc = fn(c_new.data_ptr(), k_pe_new.data_ptr(), pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), cu_q.data_ptr(), ptr(q), ptr(q_out),
             ptr(rope_table), B, total_q, Hq, P, max_pages, page, max_pos, mode, _stream())
     _raise(name, rc, "%s: max_pages * page or total_q too large for one launch" % name)
+
+
+# ---- the prompt path of multi-head latent attention: un-absorbed prefill (key 192 = 128 + 64 dims, value 128), the merge of
+# two attention states, the gather out of the latent pool
+_MLA_DN, _MLA_DQ, _MLA_DV = 128, 192, 128
+_MERGE_MAX_D = 512
+
+
+def fa2_prefill_varlen_mla_bf16(q, kv, k_pe, cu_q, cu_k, softmax_scale, out, lse=None, causal=True):
+    """Multi-head latent attention prefill (un-absorbed) of a packed batch into out: q torch.bfloat16 [total_q,Hq,192] = [q_nope 128 | q_pe 64],
+    already rotated (kv_append_paged_mla_bf16 can rotate q along the way); kv torch.bfloat16 [total_k,Hq,256] = [k_nope 128 | v 128] per head,
+    what kv_b_proj writes; k_pe torch.bfloat16 [total_k,64], rotated, one row per token shared by every head; cu_q, cu_k int32 [B+1] on the GPU
+    (never read by the host, every offset clamped): sequence b has T_b = cu_q[b+1] - cu_q[b] queries and L_b = cu_k[b+1] - cu_k[b] keys; out
+    torch.bfloat16 [total_q,Hq,128]; lse fp32 [total_q,Hq] (natural log) or None. causal=True: query t sees the keys j < L_b - (T_b - 1 - t);
+    causal=False: all L_b keys (a context chunk of a chunked prefill). A query that sees no key gets O = 0 and LSE = -inf. softmax_scale:
+    required, finite and > 0. Hq in 1 … 128. Packed rows outside [cu_q[0], cu_q[B]) are neither read nor written. Deterministic. C entry
+    cln_fa2_prefill_varlen_mla_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "fa2_prefill_varlen_mla_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 7 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_void_p])
+    scale = float(softmax_scale)
+    if not (0.0 < scale < math.inf):
+        raise RuntimeError("%s: softmax_scale %r not supported (finite and > 0; there is no default)" % (name, softmax_scale))
+    _decode_check((q, kv, k_pe, out), (cu_q, cu_k), torch.bfloat16)
+    if q.dim() != 3 or kv.dim() != 3 or k_pe.dim() != 2 or cu_q.dim() != 1:
+        raise RuntimeError("Tensor size mismatch!")
+    total_q, Hq, Dq = q.shape
+    total_k = kv.shape[0]
+    B = cu_q.shape[0] - 1
+    if Dq != _MLA_DQ:
+        raise RuntimeError("%s: q of %d dims not supported (%d = 128 nope + 64 rotary)" % (name, Dq, _MLA_DQ))
+    if B < 1 or total_q < 1 or total_k < 1:
+        raise RuntimeError("Tensor size mismatch!")
+    _check_shape(kv, total_k, Hq, _MLA_DN + _MLA_DV)
+    _check_shape(k_pe, total_k, _MLA_DR)
+    _check_shape(cu_k, B + 1)
+    _check_shape(out, total_q, Hq, _MLA_DV)
+    if Hq > _MLA_MAX_HQ:
+        raise RuntimeError("%s: %d query heads not supported (1 … %d)" % (name, Hq, _MLA_MAX_HQ))
+    lse_ptr = _decode_lse(lse, total_q, Hq)
+    rc = fn(q.data_ptr(), kv.data_ptr(), k_pe.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr(), out.data_ptr(), lse_ptr, B, total_q, total_k, Hq,
+            1 if causal else 0, scale, _stream())
+    _raise(name, rc, "%s: total_q too large for one launch" % name)
+
+
+def attn_merge_states_bf16(o_a, lse_a, o_b, lse_b, out, lse=None):
+    """Merge two attention states over disjoint key sets into out: o_a, o_b torch.bfloat16 [..., D] of one shape, lse_a, lse_b fp32 of the
+    leading shape (natural log), out torch.bfloat16 of o_a's shape (may be o_a), lse fp32 of lse_a's shape or None (may be lse_a). D % 8 == 0,
+    8 <= D <= 512. Per row in fp32: m = max(lse_a, lse_b); both -inf: O = 0, LSE = -inf; else w = exp(lse - m), a side whose LSE is -inf is
+    selected out (its O may hold anything), O = (w_a O_a + w_b O_b) / (w_a + w_b) rounded once, LSE = m + ln(w_a + w_b). Deterministic. C entry
+    cln_attn_merge_states_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "attn_merge_states_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 6 + [ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p])
+    for t in (o_a, o_b, out):
+        _check_dtype(t, torch.bfloat16)
+    for t in (lse_a, lse_b):
+        _check_dtype(t, torch.float32)
+    _check_dev(o_a, o_b, out, lse_a, lse_b)
+    if o_a.dim() < 2:
+        raise RuntimeError("Tensor size mismatch!")
+    D = o_a.shape[-1]
+    lead = tuple(o_a.shape[:-1])
+    _check_shape(o_b, *o_a.shape)
+    _check_shape(out, *o_a.shape)
+    _check_shape(lse_a, *lead)
+    _check_shape(lse_b, *lead)
+    if D % 8 != 0 or not 8 <= D <= _MERGE_MAX_D:
+        raise RuntimeError("%s: D %d not supported (a multiple of 8 in 8 … %d)" % (name, D, _MERGE_MAX_D))
+    rows = lse_a.numel()
+    if rows < 1:
+        raise RuntimeError("Tensor size mismatch!")
+    lse_ptr = _decode_lse(lse, *lead)
+    rc = fn(o_a.data_ptr(), lse_a.data_ptr(), o_b.data_ptr(), lse_b.data_ptr(), out.data_ptr(), lse_ptr, rows, D, _stream())
+    _raise(name, rc, "%s: too many rows for one launch" % name)
+
+
+def kv_gather_paged_mla_bf16(pool, block_table, cu_k, out, starts=None):
+    """Gather latent rows out of the paged latent cache of fa2_decode_paged_mla_bf16 into a packed batch: pool torch.bfloat16 [P,page,576],
+    block_table int32 [B,max_pages], cu_k int32 [B+1], starts int32 [B] or None (0), all on the GPU and never read by the host; out
+    torch.bfloat16 [total_k,576]. Packed row cu_k[b] + i receives cache row starts[b] + i of sequence b for i < cu_k[b+1] - cu_k[b], bit for
+    bit; a cache row at or past max_pages * page is written as zeros and its table entry never followed; rows of no sequence are untouched. The
+    mirror of kv_append_paged_mla_bf16. Deterministic. C entry cln_kv_gather_paged_mla_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "kv_gather_paged_mla_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_void_p])
+    _decode_check((pool, out), (block_table, cu_k) + (() if starts is None else (starts,)), torch.bfloat16)
+    if pool.dim() != 3 or block_table.dim() != 2 or out.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    P, page, _ = pool.shape
+    B, max_pages = block_table.shape
+    total_k = out.shape[0]
+    _check_shape(pool, P, page, _MLA_DK)
+    _check_shape(out, total_k, _MLA_DK)
+    _check_shape(cu_k, B + 1)
+    if starts is not None:
+        _check_shape(starts, B)
+    if page not in _PAGED_PAGES:
+        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+    rc = fn(pool.data_ptr(), block_table.data_ptr(), None if starts is None else starts.data_ptr(), cu_k.data_ptr(), out.data_ptr(), B, total_k,
+            P, max_pages, page, _stream())
+    _raise(name, rc, "%s: max_pages * page or total_k too large for one launch" % name)

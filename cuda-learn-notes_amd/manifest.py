@@ -743,6 +743,34 @@ def describe_kv_append_paged_mla_bf16(B, total_q, Hq, max_pages, page, rope_mode
     return _describe_bf16("cln_kv_append_paged_mla_bf16", tuple(int(x) for x in (B, total_q, Hq, max_pages, page)) + (mode,))
 
 
+def describe_prefill_varlen_mla_bf16(B, total_q, total_k, Hq, causal, softmax_scale):
+    """describe() for cln_fa2_prefill_varlen_mla_bf16 (include/cln_amd_ext.h): the kernel, the scale in use, the slots and the
+    grid, the LDS bytes and the MFMAs per step as text (no GPU needed). ValueError for an unsupported or invalid shape or scale (the scale is
+    required: finite and > 0)."""
+    return _describe_bf16("cln_fa2_prefill_varlen_mla_bf16", tuple(int(x) for x in (B, total_q, total_k, Hq, causal)), 2048, (float(softmax_scale),))
+
+
+def describe_attn_merge_states_bf16(rows, D):
+    """describe() for cln_attn_merge_states_bf16 (include/cln_amd_ext.h): the kernel, the launch and the rule as text (no GPU
+    needed). ValueError for an unsupported or invalid shape (D % 8 == 0, 8 <= D <= 512)."""
+    import ctypes
+    from . import _loader
+    fn = _loader.load_so("libcln_amd.so").cln_attn_merge_states_bf16_describe
+    fn.argtypes = [ctypes.c_longlong, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+    fn.restype = ctypes.c_int
+    buf = ctypes.create_string_buffer(1280)
+    rc = fn(int(rows), int(D), buf, 1280)
+    if rc < 0:
+        raise ValueError("cln_attn_merge_states_bf16: shape %s not supported (status %d)" % ((int(rows), int(D)), rc))
+    return buf.value.decode()
+
+
+def describe_kv_gather_paged_mla_bf16(B, total_k, max_pages, page):
+    """describe() for cln_kv_gather_paged_mla_bf16 (include/cln_amd_ext.h): the kernel and the launch as text (no GPU needed).
+    ValueError for an unsupported or invalid shape."""
+    return _describe_bf16("cln_kv_gather_paged_mla_bf16", tuple(int(x) for x in (B, total_k, max_pages, page)))
+
+
 def describe_kv_append_paged_varlen_bf16_fp8(B, total_q, Hq, Hkv, max_pages, page, D, rope_mode):
     """describe() for cln_kv_append_paged_varlen_bf16_fp8 (include/cln_amd_ext.h): the kernel instantiation and the launch as text (no GPU
     needed). rope_mode: 0 / "none", 1 / "half", 2 / "interleaved". ValueError for an unsupported or invalid shape."""

@@ -560,6 +560,39 @@ int cln_kv_append_paged_mla_bf16(const void* c_new, const void* k_pe_new, void* 
                                  int max_pages, int page, int max_pos, int rope_mode, void* stream);
 int cln_kv_append_paged_mla_bf16_describe(int B, int total_q, int Hq, int max_pages, int page, int rope_mode, char* buf, int len);
 
+/* ---- MLA PREFILL (un-absorbed), the merge of two attention states and the gather out of the latent pool, bf16:
+ * the prompt path in front of the two entries above. For a prompt these models up-project the latent rows with kv_b_proj and run ordinary
+ * attention per head with a key of 192 dims (128 "nope" + 64 rotary) and a value of 128, Hkv = Hq.
+ *
+ * cln_fa2_prefill_varlen_mla_bf16: a packed batch. q bf16 [total_q,Hq,192] = [q_nope 128 | q_pe 64], already rotated; kv bf16 [total_k,Hq,256] =
+ * [k_nope 128 | v 128] per head, exactly what kv_b_proj writes; k_pe bf16 [total_k,64], rotated, one row per token shared by every head (never
+ * broadcast in memory); cu_q, cu_k int32 [B+1] on the device, never read by the host, every offset clamped to [0, total_q] / [0, total_k],
+ * T_b = max(cu_q[b+1] - cu_q[b], 0), L_b likewise from cu_k; o bf16 [total_q,Hq,128]; lse fp32 [total_q,Hq], natural log, or NULL. causal = 1:
+ * query t of sequence b sees the keys j < L_b - (T_b - 1 - t); causal = 0: all L_b keys (a context chunk of a chunked prefill). A query that sees
+ * no key gets O = 0 and LSE = -inf. softmax_scale is required, finite and > 0: anything else is -1, checked first. Then -1 for a missing,
+ * misaligned (q, kv, k_pe, o 16 bytes; cu_q, cu_k, lse 4) or aliased pointer or a non-positive B, total_q, total_k or Hq; -2 for Hq > 128, a causal
+ * that is neither 0 nor 1, or a grid that does not fit. Packed rows outside [cu_q[0], cu_q[B]) are neither read nor written. No pages, window,
+ * sinks or cap. One launch, no workspace, Hq (total_q / 128 + B) workgroups; v_mfma_f32_16x16x32_bf16 with fp32 scores and accumulators, nothing
+ * passes through fp16; deterministic.
+ * cln_attn_merge_states_bf16: joins two attention states over disjoint key sets. o_a, o_b bf16 [rows,D], lse_a, lse_b fp32 [rows], o bf16
+ * [rows,D] (may be o_a), lse fp32 [rows] or NULL (may be lse_a); D % 8 == 0, 8 <= D <= 512 (else -2). Per row in fp32: m = max(lse_a, lse_b);
+ * m = -inf: O = 0, LSE = -inf; else w = exp(lse - m) per side, a side whose LSE is -inf selected out (its O may hold anything, NaN included),
+ * O = (w_a O_a + w_b O_b) / (w_a + w_b) rounded once to bf16, LSE = m + ln(w_a + w_b). One launch, deterministic.
+ * cln_kv_gather_paged_mla_bf16: pool bf16 [P,page,576], block_table int32 [B,max_pages], starts int32 [B] or NULL (0), cu_k int32 [B+1], out bf16
+ * [total_k,576]. Packed row cu_k[b] + i receives cache row starts[b] + i of sequence b for i < cu_k[b+1] - cu_k[b], bit for bit; a cache row at
+ * or past max_pages page is written as zeros and its table entry never followed; rows of no sequence are untouched. The mirror of
+ * cln_kv_append_paged_mla_bf16, with its statuses.
+ */
+int cln_fa2_prefill_varlen_mla_bf16(const void* q, const void* kv, const void* k_pe, const int* cu_q, const int* cu_k, void* o, float* lse, int B,
+                                    int total_q, int total_k, int Hq, int causal, float softmax_scale, void* stream);
+int cln_fa2_prefill_varlen_mla_bf16_describe(int B, int total_q, int total_k, int Hq, int causal, float softmax_scale, char* buf, int len);
+int cln_attn_merge_states_bf16(const void* o_a, const float* lse_a, const void* o_b, const float* lse_b, void* o, float* lse, long long rows,
+                               int D, void* stream);
+int cln_attn_merge_states_bf16_describe(long long rows, int D, char* buf, int len);
+int cln_kv_gather_paged_mla_bf16(const void* pool, const int* block_table, const int* starts, const int* cu_k, void* out, int B, int total_k,
+                                 int P, int max_pages, int page, void* stream);
+int cln_kv_gather_paged_mla_bf16_describe(int B, int total_k, int max_pages, int page, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
