@@ -488,6 +488,38 @@ def kv_gather_paged_mla_bf16(pool, block_table, cu_k, out, starts=None):
     return host.kv_gather_paged_mla_bf16(pool, block_table, cu_k, out, starts)
 
 
+def fa2_decode_paged_mla_bf16_fp8(q, pool, block_table, seqlens, kv_scale, softmax_scale, out, lse=None, workspace=None):
+    """fa2_decode_paged_mla_bf16 over a latent cache held in FP8: pool torch.float8_e4m3fn [P,page,576] of rows [c 512 | k_pe 64] in codes,
+    kv_scale fp32 [1] on the GPU (one scale for the whole pool: value = e4m3(code) * kv_scale); q bf16 [B,T,Hq,576], out bf16 [B,T,Hq,512], lse
+    fp32 [B,T,Hq] or None, softmax_scale required. The workspace is sized by fa2_decode_paged_mla_bf16_fp8_plan. C entry
+    cln_fa2_decode_paged_mla_bf16_fp8 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_decode_paged_mla_bf16_fp8(q, pool, block_table, seqlens, kv_scale, softmax_scale, out, lse, workspace)
+
+
+def fa2_decode_paged_mla_bf16_fp8_plan(B, T, Hq, max_pages, page):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_bf16_fp8: exactly fa2_decode_paged_mla_bf16_plan's. C entry
+    cln_fa2_decode_paged_mla_bf16_fp8_plan."""
+    from . import host
+    return host.fa2_decode_paged_mla_bf16_fp8_plan(B, T, Hq, max_pages, page)
+
+
+def kv_append_paged_mla_bf16_fp8(c_new, k_pe_new, pool, block_table, seqlens, cu_q, kv_scale, q=None, q_out=None, rope_table=None, rope="none"):
+    """kv_append_paged_mla_bf16 into a latent cache held in FP8: pool torch.float8_e4m3fn [P,page,576], kv_scale fp32 [1] on the GPU; the byte of
+    an element is e4m3(clamp(y * (1 / kv_scale), ±448)) in fp32, round to nearest even, y the bf16 input or the fp32 rotation result; q / q_out
+    stay bf16. C entry cln_kv_append_paged_mla_bf16_fp8 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.kv_append_paged_mla_bf16_fp8(c_new, k_pe_new, pool, block_table, seqlens, cu_q, kv_scale, q, q_out, rope_table, rope)
+
+
+def kv_gather_paged_mla_bf16_fp8(pool, block_table, cu_k, kv_scale, out, starts=None):
+    """kv_gather_paged_mla_bf16 out of a latent cache held in FP8: pool torch.float8_e4m3fn [P,page,576], kv_scale fp32 [1] on the GPU, out bf16
+    [total_k,576], each element bf16(fp32(code) * kv_scale) with one rounding. C entry cln_kv_gather_paged_mla_bf16_fp8
+    (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.kv_gather_paged_mla_bf16_fp8(pool, block_table, cu_k, kv_scale, out, starts)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

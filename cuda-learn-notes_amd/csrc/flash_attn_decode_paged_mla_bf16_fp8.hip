@@ -1,0 +1,70 @@
+// Compile unit of the multi-head latent attention (MLA) decode over a paged latent cache held in FP8 (e4m3fn) with bf16 queries:
+// cln_fa2_decode_paged_mla_bf16_fp8_plan / cln_fa2_decode_paged_mla_bf16_fp8 / cln_fa2_decode_paged_mla_bf16_fp8_describe
+// (include/cln_amd_ext.h; kernel: flash_attn_decode_paged_mla_bf16_fp8.cuh). The plan is the bf16 entry's, paged::mla_plan: the
+// key step is still 64 and D still 512. The checking order and the status codes are flash_attn_decode_paged_mla_bf16.hip's: the scale first
+// (required, finite, > 0: -1), then the pointers -- kv_scale among them, behind seqlens: missing, not 4-byte aligned or equal to an output is
+// -1 -- then P, the plan, the workspace.
+#include "flash_attn_decode_paged_mla_bf16_fp8.cuh"
+#include "paged_entry.h"
+
+static_assert(fa2b::mla8::kDc == paged::kMlaDc && fa2b::mla8::kDk == paged::kMlaDk, "paged::mla_plan sizes the workspace for this kernel's value dims");
+static_assert(fa2b::mla8::kKeyStep == paged::kMlaKeyStep && fa2b::mla8::kRowGroup == paged::kMlaRowGroup, "paged::mla_plan plans with this kernel's step and row group");
+static_assert(fa2b::mla8::kDr == paged::kMlaDr && fa2b::mla8::kLdsBytes == 75776, "the sibling's row and its one LDS image");
+
+CLN_API int cln_fa2_decode_paged_mla_bf16_fp8_plan(int B, int T, int Hq, int max_pages, int page, int* splits, int* chunk,
+                                                   long long* workspace_bytes) {
+  fa2d::PagedGeometry g;
+  fa2d::Plan p;
+  return fa2d::plan_out(paged::mla_plan(B, T, Hq, max_pages, page, &g, &p), p, splits, chunk, workspace_bytes);
+}
+
+CLN_API int cln_fa2_decode_paged_mla_bf16_fp8(const void* q, const void* pool, const int* block_table, const int* seqlens, const float* kv_scale,
+                                              void* o, float* lse, void* workspace, long long workspace_bytes, int B, int T, int Hq, int P,
+                                              int max_pages, int page, float softmax_scale, void* stream) {
+  float mult = 0.0f;
+  int rc = paged::mla_scale_arg(softmax_scale, &mult);
+  if (rc != CLN_OK) return rc;
+  const void* in[] = {q, pool, block_table, seqlens, kv_scale};  // the last three: 4-byte aligned
+  fa2d::PagedGeometry g;
+  fa2d::Plan p = {};
+  rc = fa2d::check_pointers(in, 5, 2, {o, lse, workspace});
+  if (rc != CLN_OK) return rc;
+  if (P <= 0) return CLN_ERR_BAD_ARG;
+  rc = paged::mla_plan(B, T, Hq, max_pages, page, &g, &p);
+  if (rc != CLN_OK) return rc;
+  if (!fa2d::workspace_fits(p, workspace, workspace_bytes)) return CLN_ERR_BAD_ARG;
+  const fa2b::PagedLatent8 kv = {(const unsigned char*)pool, block_table, max_pages, g.page_shift};  // the row is key and value
+  return fa2b::launch_decode_paged_mla_fp8(q, kv, seqlens, kv_scale, o, lse, workspace, B, T, Hq, p.splits, p.chunk, mult, (hipStream_t)stream);
+}
+
+CLN_API int cln_fa2_decode_paged_mla_bf16_fp8_describe(int B, int T, int Hq, int max_pages, int page, float softmax_scale, char* buf, int len) {
+  if (!buf || len <= 0) return CLN_ERR_BAD_ARG;
+  float mult = 0.0f;
+  int rc = paged::mla_scale_arg(softmax_scale, &mult);
+  if (rc != CLN_OK) return rc;
+  fa2d::PagedGeometry g;
+  fa2d::Plan p;
+  rc = paged::mla_plan(B, T, Hq, max_pages, page, &g, &p);
+  if (rc != CLN_OK) return rc;
+  const int R = T * Hq, RG = (R + paged::kMlaRowGroup - 1) / paged::kMlaRowGroup;
+  int n = snprintf(buf, len,
+                   "fa2_decode_paged_mla_bf16_fp8_mfma<Dk=%d,Dv=%d> softmax_scale=%.9g (the caller's), score multiplier x log2(e) = %.9g times "
+                   "kv_scale (fp32 [1] on the device, read once per workgroup); T=%d Hq=%d R=%d S=%d C=%d page=%d: %lld workgroups of 4 waves, one per "
+                   "(sequence, split, row group of %d query rows; %d row groups), a wave per 16-row tile (%d of the last group's 4 waves own rows); "
+                   "per %d-key step the 4 waves fetch the latent rows of e4m3fn codes [c %d | k_pe %d] (%d bytes) through the block table once, "
+                   "four lanes per row and %d 16-byte loads per lane, convert them to bf16 on the way (v_cvt_scalef32_pk_bf16_fp8, exact) and put "
+                   "them into one bf16 LDS image (%d bytes static, row stride %d bytes) that feeds both products: S^T = K Q^T from plain row reads "
+                   "over all %d dims (72 MFMAs per wave and step) and O^T = V^T P^T from transposing reads of dims 0 ... %d of the same rows (64 "
+                   "MFMAs, all 32 k-slots filled) on v_mfma_f32_16x16x32_bf16, fp32 scores and accumulators, causal mask by select, online softmax, "
+                   "P rounded once to bf16, the fp32 result times kv_scale in front of its store and O rounded once to bf16, a row that sees no key "
+                   "O = 0, LSE = -inf",
+                   paged::kMlaDk, paged::kMlaDc, (double)softmax_scale, (double)mult, T, Hq, R, p.splits, p.chunk, page, (long long)B * RG * p.splits,
+                   paged::kMlaRowGroup, RG, (R - (RG - 1) * paged::kMlaRowGroup + 15) / 16, fa2b::mla8::kKeyStep, paged::kMlaDc, paged::kMlaDr,
+                   paged::kMlaDk, fa2b::mla8::kCodeLoads, fa2b::mla8::kLdsBytes, fa2b::mla8::kRowBytes, paged::kMlaDk, paged::kMlaDc - 1);
+  if (p.splits > 1 && n < len)
+    n += snprintf(buf + n, len - n,
+                  "; then fa2_decode_combine_bf16_rows<D=%d> merges the live splits of a query row, whose partials carry kv_scale, by log-sum-exp in "
+                  "ascending order (workspace %lld bytes)", paged::kMlaDc, p.ws_bytes);
+  if (n < len) n += snprintf(buf + n, len - n, "; deterministic");
+  return n < len ? n : len - 1;
+}

@@ -1603,3 +1603,145 @@ def kv_gather_paged_mla_bf16(pool, block_table, cu_k, out, starts=None):
     rc = fn(pool.data_ptr(), block_table.data_ptr(), None if starts is None else starts.data_ptr(), cu_k.data_ptr(), out.data_ptr(), B, total_k,
             P, max_pages, page, _stream())
     _raise(name, rc, "%s: max_pages * page or total_k too large for one launch" % name)
+
+
+# ---- multi-head latent attention over a paged latent cache held in FP8: one pool torch.float8_e4m3fn [P,page,576] of rows
+# [c 512 | k_pe 64] in codes and one scale fp32 [1] on the GPU for the whole pool; everything else is bf16 as above
+def _mla_fp8_check(name, pool, kv_scale):
+    """What the MLA FP8 entries ask of the pool and its scale: a torch.float8_e4m3fn pool of three dims and an fp32 [1] scale on the GPU."""
+    _check_dtype(pool, torch.float8_e4m3fn)
+    _check_dtype(kv_scale, torch.float32)
+    _check_dev(pool, kv_scale)
+    _check_shape(kv_scale, 1)
+    if pool.dim() != 3:
+        raise RuntimeError("Tensor size mismatch!")
+
+
+def fa2_decode_paged_mla_bf16_fp8_plan(B, T, Hq, max_pages, page):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_bf16_fp8: exactly fa2_decode_paged_mla_bf16_plan's, the key step is still 64 and
+    D still 512 (cln_fa2_decode_paged_mla_bf16_fp8_plan, include/cln_amd_ext.h). T in 1 … 8, Hq in 1 … 128. No GPU needed."""
+    name = "fa2_decode_paged_mla_bf16_fp8"
+    B, T, Hq, max_pages, page = (int(x) for x in (B, T, Hq, max_pages, page))
+    rc, plan = _decode_plan("cln_%s_plan" % name, (B, T, Hq, max_pages, page))
+    if rc == -2:
+        if T > 8:
+            raise RuntimeError("%s: T %d not supported (1 … 8)" % (name, T))
+        if Hq > _MLA_MAX_HQ:
+            raise RuntimeError("%s: %d query heads not supported (1 … %d)" % (name, Hq, _MLA_MAX_HQ))
+        if page not in _PAGED_PAGES:
+            raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+        raise RuntimeError("%s: max_pages * page or B * ceil(T * Hq / 64) * splits too large for one launch" % name)
+    _raise(name, rc)
+    return plan
+
+
+def fa2_decode_paged_mla_bf16_fp8(q, pool, block_table, seqlens, kv_scale, softmax_scale, out, lse=None, workspace=None):
+    """fa2_decode_paged_mla_bf16 over a latent cache held in FP8: q torch.bfloat16 [B,T,Hq,576], absorbed; pool torch.float8_e4m3fn [P,page,576]
+    of rows [c 512 | k_pe 64] in codes; kv_scale fp32 [1] on the GPU, one scale for the whole pool: a stored byte c means e4m3(c) * kv_scale
+    (finite and > 0, no NaN byte in a live row: the caller's contract, not checked); block_table, seqlens, out torch.bfloat16 [B,T,Hq,512], lse,
+    softmax_scale (required, finite and > 0), the mask, T in 1 … 8, Hq in 1 … 128 and the pages as there. The codes are converted to bf16
+    exactly on the way to LDS; the fp32 score multiplier is (softmax_scale * log2(e)) * kv_scale and kv_scale multiplies the fp32 result in front
+    of its store. workspace: at least fa2_decode_paged_mla_bf16_fp8_plan(...)[2] bytes; allocated here when None and the plan splits the keys.
+    Deterministic. C entry cln_fa2_decode_paged_mla_bf16_fp8 (include/cln_amd_ext.h); no CPU path."""
+    name = "fa2_decode_paged_mla_bf16_fp8"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 8 + [ctypes.c_longlong] + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_void_p])
+    scale = float(softmax_scale)
+    if not (0.0 < scale < math.inf):
+        raise RuntimeError("%s: softmax_scale %r not supported (finite and > 0; there is no default)" % (name, softmax_scale))
+    _decode_check((q, out), (block_table, seqlens), torch.bfloat16)
+    _mla_fp8_check(name, pool, kv_scale)
+    if q.dim() != 4 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    B, T, Hq, Dk = q.shape
+    P, page, _ = pool.shape
+    if Dk != _MLA_DK:
+        raise RuntimeError("%s: q of %d dims not supported (%d = 512 latent + 64 rotary)" % (name, Dk, _MLA_DK))
+    _check_shape(pool, P, page, _MLA_DK)
+    if block_table.shape[0] != B:
+        raise RuntimeError("Tensor size mismatch!")
+    max_pages = block_table.shape[1]
+    _check_shape(out, B, T, Hq, _MLA_DC)
+    _check_shape(seqlens, B)
+    lse_ptr = _decode_lse(lse, B, T, Hq)
+    ws_ptr, ws_bytes = _decode_workspace(name, fa2_decode_paged_mla_bf16_fp8_plan(B, T, Hq, max_pages, page)[2], workspace, q.device)
+    rc = fn(q.data_ptr(), pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), kv_scale.data_ptr(), out.data_ptr(), lse_ptr, ws_ptr,
+            ws_bytes, B, T, Hq, P, max_pages, page, scale, _stream())
+    _raise(name, rc)
+
+
+def kv_append_paged_mla_bf16_fp8(c_new, k_pe_new, pool, block_table, seqlens, cu_q, kv_scale, q=None, q_out=None, rope_table=None, rope="none"):
+    """kv_append_paged_mla_bf16 into a latent cache held in FP8; one launch. c_new torch.bfloat16 [total_q,512], k_pe_new torch.bfloat16
+    [total_q,64]; pool torch.float8_e4m3fn [P,page,576], written in place; kv_scale fp32 [1] on the GPU. Per element of a live pool row the byte
+    is e4m3(clamp(y * (1 / kv_scale), ±448)) in fp32, round to nearest even, y the bf16 input or the fp32 rotation result with no bf16 rounding
+    in between. q, q_out torch.bfloat16 [total_q,Hq,576] (q_out may be q), cu_q, block_table, seqlens, rope_table, the three rope modes, liveness
+    and the untouched rows of no sequence as there. Deterministic. C entry cln_kv_append_paged_mla_bf16_fp8 (include/cln_amd_ext.h); no CPU
+    path."""
+    name = "kv_append_paged_mla_bf16_fp8"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 10 + [ctypes.c_int] * 8 + [ctypes.c_void_p])
+    if rope not in _ROPE_MODES:
+        raise RuntimeError("%s: rope %r not supported ('none', 'half' or 'interleaved')" % (name, rope))
+    mode = _ROPE_MODES[rope]
+    if mode == 0 and rope_table is not None:
+        raise RuntimeError("%s: rope 'none' takes no rope_table" % name)
+    if mode != 0 and rope_table is None:
+        raise RuntimeError("%s: rope %r needs a rope_table (kv_append_rope_table(max_pos, 64))" % (name, rope))
+    if (q is None) != (q_out is None):
+        raise RuntimeError("%s: q and q_out are given together or not at all" % name)
+    _decode_check((c_new, k_pe_new) + ((q, q_out) if q is not None else ()), (block_table, seqlens, cu_q), torch.bfloat16)
+    _mla_fp8_check(name, pool, kv_scale)
+    if c_new.dim() != 2 or k_pe_new.dim() != 2 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    total_q = c_new.shape[0]
+    P, page, _ = pool.shape
+    B, max_pages = block_table.shape
+    _check_shape(c_new, total_q, _MLA_DC)
+    _check_shape(k_pe_new, total_q, _MLA_DR)
+    _check_shape(pool, P, page, _MLA_DK)
+    _check_shape(seqlens, B)
+    _check_shape(cu_q, B + 1)
+    Hq, max_pos = 1, 0
+    if q is not None:
+        if q.dim() != 3:
+            raise RuntimeError("Tensor size mismatch!")
+        Hq = q.shape[1]
+        _check_shape(q, total_q, Hq, _MLA_DK)
+        _check_shape(q_out, total_q, Hq, _MLA_DK)
+    if rope_table is not None:
+        _check_dtype(rope_table, torch.float32)
+        _check_dev(rope_table)
+        if rope_table.dim() != 2:
+            raise RuntimeError("Tensor size mismatch!")
+        max_pos = rope_table.shape[0]
+        _check_shape(rope_table, max_pos, _MLA_DR)
+    if page not in _PAGED_PAGES:
+        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    rc = fn(c_new.data_ptr(), k_pe_new.data_ptr(), pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), cu_q.data_ptr(),
+            kv_scale.data_ptr(), ptr(q), ptr(q_out), ptr(rope_table), B, total_q, Hq, P, max_pages, page, max_pos, mode, _stream())
+    _raise(name, rc, "%s: max_pages * page or total_q too large for one launch" % name)
+
+
+def kv_gather_paged_mla_bf16_fp8(pool, block_table, cu_k, kv_scale, out, starts=None):
+    """kv_gather_paged_mla_bf16 out of a latent cache held in FP8: pool torch.float8_e4m3fn [P,page,576], kv_scale fp32 [1] on the GPU, out
+    torch.bfloat16 [total_k,576]; each element is bf16(fp32(code) * kv_scale), one rounding. block_table, cu_k, starts, the zeros for a cache row
+    at or past max_pages * page and the untouched rows of no sequence as there: the context-chunk loop of the prompt path runs unchanged over an
+    FP8 pool. Deterministic. C entry cln_kv_gather_paged_mla_bf16_fp8 (include/cln_amd_ext.h); no CPU path."""
+    name = "kv_gather_paged_mla_bf16_fp8"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 5 + [ctypes.c_void_p])
+    _decode_check((out,), (block_table, cu_k) + (() if starts is None else (starts,)), torch.bfloat16)
+    _mla_fp8_check(name, pool, kv_scale)
+    if block_table.dim() != 2 or out.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    P, page, _ = pool.shape
+    B, max_pages = block_table.shape
+    total_k = out.shape[0]
+    _check_shape(pool, P, page, _MLA_DK)
+    _check_shape(out, total_k, _MLA_DK)
+    _check_shape(cu_k, B + 1)
+    if starts is not None:
+        _check_shape(starts, B)
+    if page not in _PAGED_PAGES:
+        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+    rc = fn(pool.data_ptr(), block_table.data_ptr(), None if starts is None else starts.data_ptr(), cu_k.data_ptr(), kv_scale.data_ptr(),
+            out.data_ptr(), B, total_k, P, max_pages, page, _stream())
+    _raise(name, rc, "%s: max_pages * page or total_k too large for one launch" % name)

@@ -771,6 +771,28 @@ def describe_kv_gather_paged_mla_bf16(B, total_k, max_pages, page):
     return _describe_bf16("cln_kv_gather_paged_mla_bf16", tuple(int(x) for x in (B, total_k, max_pages, page)))
 
 
+def describe_decode_paged_mla_bf16_fp8(B, T, Hq, max_pages, page, softmax_scale):
+    """describe() for cln_fa2_decode_paged_mla_bf16_fp8 (include/cln_amd_ext.h): the text of the bf16 MLA entry with the stage of
+    e4m3fn codes, the conversion, the LDS bytes and where kv_scale enters (no GPU needed). ValueError for an unsupported or invalid shape or
+    scale (the scale is required: finite and > 0)."""
+    return _describe_bf16("cln_fa2_decode_paged_mla_bf16_fp8", tuple(int(x) for x in (B, T, Hq, max_pages, page)), 3072, (float(softmax_scale),))
+
+
+def describe_kv_append_paged_mla_bf16_fp8(B, total_q, Hq, max_pages, page, rope_mode):
+    """describe() for cln_kv_append_paged_mla_bf16_fp8 (include/cln_amd_ext.h): the kernel instantiation, the launch and the
+    quantiser as text (no GPU needed). rope_mode: 0 / "none", 1 / "half", 2 / "interleaved". ValueError for an unsupported or invalid shape."""
+    mode = {"none": 0, "half": 1, "interleaved": 2}.get(rope_mode, rope_mode)
+    if not isinstance(mode, int):
+        raise ValueError("cln_kv_append_paged_mla_bf16_fp8: rope %r not supported" % (rope_mode,))
+    return _describe_bf16("cln_kv_append_paged_mla_bf16_fp8", tuple(int(x) for x in (B, total_q, Hq, max_pages, page)) + (mode,), 2048)
+
+
+def describe_kv_gather_paged_mla_bf16_fp8(B, total_k, max_pages, page):
+    """describe() for cln_kv_gather_paged_mla_bf16_fp8 (include/cln_amd_ext.h): the kernel, the launch and the dequantising load
+    as text (no GPU needed). ValueError for an unsupported or invalid shape."""
+    return _describe_bf16("cln_kv_gather_paged_mla_bf16_fp8", tuple(int(x) for x in (B, total_k, max_pages, page)), 2048)
+
+
 def describe_kv_append_paged_varlen_bf16_fp8(B, total_q, Hq, Hkv, max_pages, page, D, rope_mode):
     """describe() for cln_kv_append_paged_varlen_bf16_fp8 (include/cln_amd_ext.h): the kernel instantiation and the launch as text (no GPU
     needed). rope_mode: 0 / "none", 1 / "half", 2 / "interleaved". ValueError for an unsupported or invalid shape."""

@@ -593,6 +593,36 @@ int cln_kv_gather_paged_mla_bf16(const void* pool, const int* block_table, const
                                  int P, int max_pages, int page, void* stream);
 int cln_kv_gather_paged_mla_bf16_describe(int B, int total_k, int max_pages, int page, char* buf, int len);
 
+/* ---- MLA over a paged latent cache held in FP8 (OCP e4m3fn), bf16 queries: the three entries above that touch the
+ * pool, on a pool of codes. pool [P, page, 576] of bytes, a row [c (512) | k_pe (64)] in codes, 576 bytes; kv_scale fp32 [1] ON THE DEVICE, one
+ * scale for the whole row: value = e4m3(code) kv_scale. The caller guarantees a finite kv_scale > 0 and no NaN code (0x7f, 0xff) in a live row;
+ * the kernels do not check either. block_table, seqlens, cu_q, cu_k, starts, the page sizes and max_pages page < 2^31 are the bf16 entries'; q,
+ * q_out, c_new, k_pe_new, o and the gather's out stay bf16. Arguments, checks and status codes are the bf16 entries', in their order; kv_scale
+ * stands behind seqlens (append: cu_q, gather: cu_k) and a missing one, one not 4-byte aligned or one equal to an output is -1 there, before
+ * the shape. The decode's softmax_scale check stays first.
+ *
+ * cln_kv_append_paged_mla_bf16_fp8: cln_kv_append_paged_mla_bf16 with a quantising store. Per element of a live pool row, in fp32:
+ * byte = e4m3(clamp(y (1.0f / kv_scale), +-448)), round to nearest even, y the bf16 input or the fp32 rotation result with no bf16 rounding in
+ * between. q / q_out as there, bf16.
+ * cln_fa2_decode_paged_mla_bf16_fp8: cln_fa2_decode_paged_mla_bf16 on the dequantised pool. The codes are converted to bf16 exactly on the way
+ * to LDS, once per workgroup; the fp32 score multiplier is (softmax_scale log2 e) kv_scale and kv_scale multiplies the fp32 result in front of
+ * its store, so the partials of a split carry it. _plan returns what cln_fa2_decode_paged_mla_bf16_plan returns, status included.
+ * cln_kv_gather_paged_mla_bf16_fp8: cln_kv_gather_paged_mla_bf16 with a dequantising load; an element of out is bf16(fp32(code) kv_scale), one
+ * rounding.
+ */
+int cln_kv_append_paged_mla_bf16_fp8(const void* c_new, const void* k_pe_new, void* pool, const int* block_table, const int* seqlens,
+                                     const int* cu_q, const float* kv_scale, const void* q, void* q_out, const float* rope_table, int B,
+                                     int total_q, int Hq, int P, int max_pages, int page, int max_pos, int rope_mode, void* stream);
+int cln_kv_append_paged_mla_bf16_fp8_describe(int B, int total_q, int Hq, int max_pages, int page, int rope_mode, char* buf, int len);
+int cln_fa2_decode_paged_mla_bf16_fp8_plan(int B, int T, int Hq, int max_pages, int page, int* splits, int* chunk, long long* workspace_bytes);
+int cln_fa2_decode_paged_mla_bf16_fp8(const void* q, const void* pool, const int* block_table, const int* seqlens, const float* kv_scale, void* o,
+                                      float* lse, void* workspace, long long workspace_bytes, int B, int T, int Hq, int P, int max_pages,
+                                      int page, float softmax_scale, void* stream);
+int cln_fa2_decode_paged_mla_bf16_fp8_describe(int B, int T, int Hq, int max_pages, int page, float softmax_scale, char* buf, int len);
+int cln_kv_gather_paged_mla_bf16_fp8(const void* pool, const int* block_table, const int* starts, const int* cu_k, const float* kv_scale,
+                                     void* out, int B, int total_k, int P, int max_pages, int page, void* stream);
+int cln_kv_gather_paged_mla_bf16_fp8_describe(int B, int total_k, int max_pages, int page, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
