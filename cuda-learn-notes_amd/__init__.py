@@ -520,6 +520,24 @@ def kv_gather_paged_mla_bf16_fp8(pool, block_table, cu_k, kv_scale, out, starts=
     return host.kv_gather_paged_mla_bf16_fp8(pool, block_table, cu_k, kv_scale, out, starts)
 
 
+def fa2_decode_paged_mla_sparse_bf16(q, pool, block_table, seqlens, indices, softmax_scale, out, lse=None, workspace=None):
+    """Sparse MLA decode (DeepSeek-V3.2) over the paged latent cache of fa2_decode_paged_mla_bf16: q bf16 [B,T,Hq,576] absorbed, pool bf16
+    [P,page,576], out bf16 [B,T,Hq,512], lse fp32 [B,T,Hq] or None, softmax_scale required, any T >= 1. indices int32 [B,T,topk] on the GPU: per
+    query token the logical token positions it attends to, shared by its heads; a slot is valid iff 0 <= idx < seqlens[b] - (T - 1 - t) (the
+    length clamped to the cache), every other value (-1 …) is an empty slot that may stand anywhere. Pass distinct positions: one listed twice is
+    two keys. No valid slot: O = 0, LSE = -inf. The workspace is sized by fa2_decode_paged_mla_sparse_bf16_plan. C entry
+    cln_fa2_decode_paged_mla_sparse_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_decode_paged_mla_sparse_bf16(q, pool, block_table, seqlens, indices, softmax_scale, out, lse, workspace)
+
+
+def fa2_decode_paged_mla_sparse_bf16_plan(B, T, Hq, topk, max_pages, page):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_sparse_bf16: the splits divide the topk index slots of a query token. C entry
+    cln_fa2_decode_paged_mla_sparse_bf16_plan."""
+    from . import host
+    return host.fa2_decode_paged_mla_sparse_bf16_plan(B, T, Hq, topk, max_pages, page)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

@@ -312,6 +312,18 @@ inline int mla_plan(int B, int T, int Hq, int max_pages, int page, fa2d::PagedGe
   const long long R = (long long)T * Hq, row_groups = (R + kMlaRowGroup - 1) / kMlaRowGroup;
   return fa2d::split_plan(B * row_groups, B * R, g->Nmax, page > kMlaKeyStep ? page : kMlaKeyStep, kMlaDc, p);
 }
+// The split plan of the SPARSE decode (the *_mla_sparse_* entries): a workgroup serves one (sequence, query token, group of 64
+// heads, split of the token's topk index slots), so fa2d::split_plan(bk = B T ceil(Hq / 64), rows = B T Hq, Nmax = topk, unit = 64, D = 512):
+// the splits divide the index slots, not the context, and T has no cap. -1 for a non-positive dimension, -2 for Hq > 128, another page,
+// max_pages page >= 2^31, B T Hq >= 2^31 or a grid that does not fit.
+inline int mla_sparse_plan(int B, int T, int Hq, int topk, int max_pages, int page, fa2d::PagedGeometry* g, fa2d::Plan* p) {
+  if (B <= 0 || T <= 0 || Hq <= 0 || topk <= 0) return CLN_ERR_BAD_ARG;
+  const int rc = fa2d::paged_geometry(1, 1, max_pages, page, g);
+  if (rc != CLN_OK) return rc;
+  const long long tokens = (long long)B * T;
+  if (Hq > kMlaMaxHq || tokens > 0x7fffffffLL) return CLN_ERR_UNSUPPORTED;
+  return fa2d::split_plan(tokens * ((Hq + kMlaRowGroup - 1) / kMlaRowGroup), tokens * Hq, topk, kMlaKeyStep, kMlaDc, p);
+}
 // The append: a thread per 16-byte piece; per token one pool row and, with q, Hq query rows of 64 copied pieces and the rotary pieces (4 with
 // the half-split pairs, which a thread moves two at a time, else 8). *y = the workgroups per token.
 inline int mla_append_pieces(int rope_mode) { return kMlaDc / 8 + (rope_mode == 1 ? kMlaDr / 16 : kMlaDr / 8); }

@@ -1745,3 +1745,62 @@ def kv_gather_paged_mla_bf16_fp8(pool, block_table, cu_k, kv_scale, out, starts=
     rc = fn(pool.data_ptr(), block_table.data_ptr(), None if starts is None else starts.data_ptr(), cu_k.data_ptr(), kv_scale.data_ptr(),
             out.data_ptr(), B, total_k, P, max_pages, page, _stream())
     _raise(name, rc, "%s: max_pages * page or total_k too large for one launch" % name)
+
+
+# ---- sparse multi-head latent attention over the paged latent cache: DeepSeek-V3.2's attention behind its indexer. The pool,
+# the table, the lengths and the absorbed q are fa2_decode_paged_mla_bf16's; every query token brings its own list of cache positions
+def fa2_decode_paged_mla_sparse_bf16_plan(B, T, Hq, topk, max_pages, page):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_sparse_bf16: a function of the shape only; the splits divide the topk index slots
+    of a query token, not the context (cln_fa2_decode_paged_mla_sparse_bf16_plan, include/cln_amd_ext.h). T >= 1 (no cap: a query token is its
+    own workgroup job), Hq in 1 … 128, topk >= 1. No GPU needed."""
+    name = "fa2_decode_paged_mla_sparse_bf16"
+    B, T, Hq, topk, max_pages, page = (int(x) for x in (B, T, Hq, topk, max_pages, page))
+    rc, plan = _decode_plan("cln_%s_plan" % name, (B, T, Hq, topk, max_pages, page))
+    if rc == -2:
+        if Hq > _MLA_MAX_HQ:
+            raise RuntimeError("%s: %d query heads not supported (1 … %d)" % (name, Hq, _MLA_MAX_HQ))
+        if page not in _PAGED_PAGES:
+            raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+        raise RuntimeError("%s: max_pages * page, B * T * Hq or B * T * ceil(Hq / 64) * splits too large for one launch" % name)
+    _raise(name, rc)
+    return plan
+
+
+def fa2_decode_paged_mla_sparse_bf16(q, pool, block_table, seqlens, indices, softmax_scale, out, lse=None, workspace=None):
+    """Sparse MLA decode (DeepSeek-V3.2, "DSA") over the paged latent cache; bf16. q torch.bfloat16 [B,T,Hq,576], absorbed; pool torch.bfloat16
+    [P,page,576] of rows [c 512 | k_pe 64]; block_table int32 [B,max_pages]; seqlens int32 [B]; out torch.bfloat16 [B,T,Hq,512]; lse fp32 [B,T,Hq]
+    or None: all as in fa2_decode_paged_mla_bf16. indices int32 [B,T,topk], contiguous, on the GPU, never read by the host: slot k of
+    indices[b,t] is a LOGICAL token position of sequence b (the position space of seqlens), resolved through the block table, shared by all heads
+    of that token. A slot is valid iff 0 <= idx < vis(b,t) = clamp(seqlens[b], 0, max_pages * page) - (T - 1 - t); every other value (-1, any
+    negative, anything at or past vis) is an empty slot, anywhere in the list, and addresses nothing. Over the valid slots V of a token:
+    s_k = softmax_scale * q . row(idx_k), O = softmax_V(s) row[:, 0:512], LSE = ln sum_V exp(s_k); V empty: O = 0, LSE = -inf. A position listed
+    twice is two keys: pass distinct positions. softmax_scale required, finite and > 0; Hq in 1 … 128; any T >= 1 (also V3.2's sparse prefill
+    over the paged cache); any topk >= 1. workspace: at least fa2_decode_paged_mla_sparse_bf16_plan(...)[2] bytes; allocated here when None and
+    the plan splits the list. Deterministic. C entry cln_fa2_decode_paged_mla_sparse_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "fa2_decode_paged_mla_sparse_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 8 + [ctypes.c_longlong] + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_void_p])
+    scale = float(softmax_scale)
+    if not (0.0 < scale < math.inf):
+        raise RuntimeError("%s: softmax_scale %r not supported (finite and > 0; there is no default)" % (name, softmax_scale))
+    _decode_check((q, pool, out), (block_table, seqlens, indices), torch.bfloat16)
+    if q.dim() != 4 or pool.dim() != 3 or block_table.dim() != 2 or indices.dim() != 3:
+        raise RuntimeError("Tensor size mismatch!")
+    B, T, Hq, Dk = q.shape
+    P, page, _ = pool.shape
+    topk = indices.shape[2]
+    if Dk != _MLA_DK:
+        raise RuntimeError("%s: q of %d dims not supported (%d = 512 latent + 64 rotary)" % (name, Dk, _MLA_DK))
+    _check_shape(pool, P, page, _MLA_DK)
+    if block_table.shape[0] != B:
+        raise RuntimeError("Tensor size mismatch!")
+    max_pages = block_table.shape[1]
+    _check_shape(out, B, T, Hq, _MLA_DC)
+    _check_shape(seqlens, B)
+    _check_shape(indices, B, T, topk)
+    if not indices.is_contiguous():
+        raise RuntimeError("%s: indices must be contiguous [B,T,topk]" % name)
+    lse_ptr = _decode_lse(lse, B, T, Hq)
+    ws_ptr, ws_bytes = _decode_workspace(name, fa2_decode_paged_mla_sparse_bf16_plan(B, T, Hq, topk, max_pages, page)[2], workspace, q.device)
+    rc = fn(q.data_ptr(), pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), indices.data_ptr(), out.data_ptr(), lse_ptr, ws_ptr,
+            ws_bytes, B, T, Hq, topk, P, max_pages, page, scale, _stream())
+    _raise(name, rc)

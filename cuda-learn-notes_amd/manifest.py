@@ -778,6 +778,14 @@ def describe_decode_paged_mla_bf16_fp8(B, T, Hq, max_pages, page, softmax_scale)
     return _describe_bf16("cln_fa2_decode_paged_mla_bf16_fp8", tuple(int(x) for x in (B, T, Hq, max_pages, page)), 3072, (float(softmax_scale),))
 
 
+def describe_decode_paged_mla_sparse_bf16(B, T, Hq, topk, max_pages, page, softmax_scale):
+    """describe() for cln_fa2_decode_paged_mla_sparse_bf16 (include/cln_amd_ext.h): the kernel, the scale in use, the jobs and the
+    split of the index list, the indirection, the LDS bytes, the MFMA counts and the combine as text (no GPU needed). ValueError for an
+    unsupported or invalid shape or scale (the scale is required: finite and > 0)."""
+    return _describe_bf16("cln_fa2_decode_paged_mla_sparse_bf16", tuple(int(x) for x in (B, T, Hq, topk, max_pages, page)), 3072,
+                          (float(softmax_scale),))
+
+
 def describe_kv_append_paged_mla_bf16_fp8(B, total_q, Hq, max_pages, page, rope_mode):
     """describe() for cln_kv_append_paged_mla_bf16_fp8 (include/cln_amd_ext.h): the kernel instantiation, the launch and the
     quantiser as text (no GPU needed). rope_mode: 0 / "none", 1 / "half", 2 / "interleaved". ValueError for an unsupported or invalid shape."""

@@ -623,6 +623,30 @@ int cln_kv_gather_paged_mla_bf16_fp8(const void* pool, const int* block_table, c
                                      void* out, int B, int total_k, int P, int max_pages, int page, void* stream);
 int cln_kv_gather_paged_mla_bf16_fp8_describe(int B, int total_k, int max_pages, int page, char* buf, int len);
 
+/* ---- Sparse MLA decode over the paged latent cache, bf16: DeepSeek-V3.2's attention ("DSA") behind its indexer.
+ * q [B,T,Hq,576], pool [P,page,576], block_table [B,max_pages], seqlens [B], o [B,T,Hq,512], lse fp32 [B,T,Hq] or null, softmax_scale
+ * (required, finite, > 0) are cln_fa2_decode_paged_mla_bf16's. indices int32 [B,T,topk], contiguous, ON THE DEVICE, 4-byte aligned, never read
+ * by the host: slot k of indices[b,t] is a LOGICAL token position of sequence b (the position space of seqlens), resolved through the block
+ * table, the same list for all heads of the token. A slot is VALID iff 0 <= idx < vis(b,t) = clamp(seqlens[b], 0, max_pages page) - (T - 1 - t),
+ * the dense entry's causal edge; every other value -- -1, any negative, anything at or past vis or past the cache -- is an EMPTY slot, may
+ * stand anywhere in the list, and addresses no table entry and no pool row. With V the valid slots of a query token all its heads compute
+ * s_k = softmax_scale q . row(idx_k)[0:576], O = softmax_V(s) row[:, 0:512], LSE = ln sum_V exp(s_k); V empty: O = 0, LSE = -inf exactly. A
+ * position listed twice is two keys: pass distinct positions. Hq in 1 ... 128; topk >= 1, any value; T >= 1 WITHOUT the cap of 8 (a query
+ * token is its own workgroup job: the entry is V3.2's sparse prefill over the paged cache too).
+ * Status, in this order: the scale (-1); a missing or misaligned pointer (q, pool, o, lse, workspace 16 bytes; block_table, seqlens, indices
+ * 4 bytes) or an output equal to an input or another output (-1); P <= 0 (-1); the plan -- a non-positive B, T, Hq, topk, max_pages or page
+ * (-1), Hq > 128, another page, max_pages page >= 2^31, B T Hq >= 2^31 or a grid that does not fit (-2); a workspace smaller than the plan's
+ * (-1). _plan: a function of the shape only; the splits divide the topk index slots (chunk a multiple of 64), workspace_bytes =
+ * B T Hq splits (512 + 2) 4 when splits > 1, else 0. Every split of a row is written and all are merged in ascending order: deterministic.
+ */
+int cln_fa2_decode_paged_mla_sparse_bf16_plan(int B, int T, int Hq, int topk, int max_pages, int page, int* splits, int* chunk,
+                                              long long* workspace_bytes);
+int cln_fa2_decode_paged_mla_sparse_bf16(const void* q, const void* pool, const int* block_table, const int* seqlens, const int* indices, void* o,
+                                         float* lse, void* workspace, long long workspace_bytes, int B, int T, int Hq, int topk, int P,
+                                         int max_pages, int page, float softmax_scale, void* stream);
+int cln_fa2_decode_paged_mla_sparse_bf16_describe(int B, int T, int Hq, int topk, int max_pages, int page, float softmax_scale, char* buf,
+                                                  int len);
+
 #ifdef __cplusplus
 }
 #endif
