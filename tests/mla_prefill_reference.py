@@ -15,6 +15,7 @@ paged_bf16_reference.o_bound(emul, ref), LSE within decode_reference.lse_tol, -i
 
 A plain module: nothing here is collected. Cases are made on the CPU, once per process, and never modified."""
 import functools
+import math
 
 import torch
 
@@ -26,6 +27,10 @@ MAX_HQ = 128
 LOG2E = cr.LOG2E
 NEG_INF = float("-inf")
 SCALE = 192 ** -0.5
+YARN = SCALE * (0.1 * math.log(40) + 1) ** 2  # DeepSeek-V3 / R1 with YaRN (mscale^2 at factor 40): about 0.1353
+QUARTER = SCALE / 4
+OTHER_SCALES = (YARN, QUARTER)  # scales that are not the test data's
+Q_MULT = 1  # q and the keys are standard normal: the scores have standard deviation 1 at SCALE and the softmax is far from flat as it is
 
 
 # ---------------------------------------------------------------------------------------------------- reference and emulation
@@ -150,3 +155,11 @@ def packed_case(Ts, Ls, Hq, seed=0, front=0, back=0):
 
 def one_case(T, ctx, Hq):
     return packed_case((T,), (T + ctx,), Hq)
+
+
+@functools.lru_cache(maxsize=None)
+def scale_case(causal, scale, Hq=3):
+    """(q, kv, k_pe, cu_q, cu_k, the reference at scale, the reference at SCALE) of the ragged packed batch of the GPU test."""
+    Ts, Ls = tuple(RAGGED_T + SHORT_T), tuple(RAGGED_L + SHORT_L)
+    q, kv, k_pe, cu_q, cu_k = packed_case(Ts, Ls, Hq, seed=1, front=FRONT, back=BACK)
+    return q, kv, k_pe, cu_q, cu_k, prefill(q, kv, k_pe, cu_q, cu_k, scale, causal), prefill(q, kv, k_pe, cu_q, cu_k, SCALE, causal)

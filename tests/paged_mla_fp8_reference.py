@@ -152,3 +152,11 @@ def parity_cases():
 def all_finite_codes():
     """The 254 finite e4m3fn codes as uint8, subnormals and -0 included: every byte but 0x7f and 0xff."""
     return torch.tensor([c for c in range(256) if c & 0x7F != 0x7F], dtype=torch.uint8)
+
+
+@functools.lru_cache(maxsize=None)
+def scale_case(T, Hq, split, kv_scale, scale):
+    """paged_mla_reference.scale_case over the pool of codes at kv_scale."""
+    q, lens, pool = split_case(T, Hq, kv_scale) if split else one_case(T, Hq, 16, kv_scale)
+    q = ml.times(q, ml.Q_MULT)
+    return q, lens, pool, decode(q, *pool, lens, kv_scale, scale), decode(q, *pool, lens, kv_scale, SCALE)

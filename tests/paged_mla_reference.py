@@ -14,6 +14,7 @@ tolerance: O within paged_bf16_reference.o_bound(emul, ref), LSE within decode_r
 
 A plain module: nothing here is collected. Cases are made on the CPU, once per process, and never modified."""
 import functools
+import math
 
 import torch
 
@@ -28,6 +29,14 @@ NEG_INF = float("-inf")
 INT_MAX = 2 ** 31 - 1
 SCALE = 192 ** -0.5   # the models' scale without mscale, and the scale of the test data
 FILL = 2.0 ** 100     # what the pages no live table entry names hold
+YARN = SCALE * (0.1 * math.log(40) + 1) ** 2  # DeepSeek-V3 / R1 with YaRN (mscale^2 at factor 40): about 0.1353
+QUARTER = SCALE / 4
+OTHER_SCALES = (YARN, QUARTER)  # scales that are not the test data's
+# q and the rows are N(0, 1 / 192): q . row has standard deviation 0.125 and the scores, under any of the scales, 0.02 at the most -- a softmax
+# too flat to tell one scale from another. q x 2^7 (exact in bf16) is the smallest power of two at which every (3, 5) and (2, 40) case of the
+# three decode entries, at both KV_SCALES, meets sees_the_scale() at both OTHER_SCALES; found on the CPU, asserted by the surface tests.
+Q_MULT = 128
+SENSITIVITY = 20
 
 
 # ---------------------------------------------------------------------------------------------------- reference and emulation
@@ -146,3 +155,32 @@ def split_case(T, Hq):
     """case 2: (q [5,T,Hq,576], lens, (pool, block_table)); Nmax 1024 at page 16."""
     q = _randn((len(SPLIT_LENS), T, Hq, DK), torch.Generator().manual_seed(1000 * T + Hq))
     return q, SPLIT_LENS, make_pool(_dense(len(SPLIT_LENS), SPLIT_PAGE * SPLIT_MAX_PAGES), SPLIT_PAGE, SPLIT_LENS, seed=Hq)
+
+
+# ---------------------------------------------------------------------------------------------------- a scale that is not the data's
+
+def times(q, mult):
+    """q x a power of two, exact in bf16."""
+    out = (q.float() * mult).to(BF)
+    assert torch.equal(out.float(), q.float() * mult)
+    return out
+
+
+def sees_the_scale(ref, ref_at_data_scale):
+    """(max |O_ref(scale) - O_ref(SCALE)|, SENSITIVITY x o_bound at scale): a kernel that ran at SCALE whatever it was given is far outside
+    the bound iff the first exceeds the second (test_rotary_dims_reach_the_scores' condition)."""
+    import paged_bf16_reference as br
+    ro, _, emul = ref
+    fin = torch.isfinite(ro)
+    return float((ro[fin] - ref_at_data_scale[0][fin]).abs().max()), SENSITIVITY * br.o_bound(emul, ro)
+
+
+SCALE_TH = [(3, 5, False), (2, 40, True)]  # (T, Hq, several splits): one_case at page 16 and split_case
+
+
+@functools.lru_cache(maxsize=None)
+def scale_case(T, Hq, split, scale):
+    """(q x Q_MULT, lens, (pool, block_table), the reference at scale, the reference at SCALE) of one_case(T, Hq, 16) or split_case(T, Hq)."""
+    q, lens, pool = split_case(T, Hq) if split else one_case(T, Hq, 16)
+    q = times(q, Q_MULT)
+    return q, lens, pool, decode(q, *pool, lens, scale), decode(q, *pool, lens, SCALE)

@@ -163,3 +163,13 @@ def many_case(T, Hq):
     q = _randn((len(MANY_LENS), T, Hq, DK), torch.Generator().manual_seed(10 * T + Hq))
     pool = ml.make_pool(_dense(len(MANY_LENS), Nmax), MANY_PAGE, MANY_LENS, seed=T)
     return q, MANY_LENS, pool, sample_indices(MANY_LENS, T, Nmax, MANY_TOPK, seed=T + Hq)
+
+
+@functools.lru_cache(maxsize=None)
+def scale_case(T, Hq, split, scale):
+    """paged_mla_reference.scale_case for the sparse entry: (q x Q_MULT, lens, (pool, block_table), indices, the reference at scale, the
+    reference at SCALE) of one_case(T, Hq, 16) at topk 200 or split_case(T, Hq) at topk 2048."""
+    q, lens, pool = split_case(T, Hq) if split else one_case(T, Hq, 16)
+    idx = split_indices(T, Hq, True) if split else one_indices(T, Hq, 16, 200)
+    q = ml.times(q, ml.Q_MULT)
+    return q, lens, pool, idx, decode_sparse(q, *pool, lens, idx, scale), decode_sparse(q, *pool, lens, idx, SCALE)

@@ -125,6 +125,19 @@ def test_packed_ragged_batch(built, dev, causal):
     assert same((again[0][seq], again[1][seq]), (got[0][seq], got[1][seq]))
 
 
+@pytest.mark.parametrize("scale", mp.OTHER_SCALES, ids=["yarn", "quarter"])
+@pytest.mark.parametrize("causal", [True, False], ids=["causal", "non-causal"])
+def test_packed_ragged_batch_at_a_scale_that_is_not_the_datas(built, dev, causal, scale):
+    """The ragged packed batch at V3's YaRN scale and at SCALE / 4: the reference at SCALE is more than 20 x o_bound away (proven without a
+    GPU by tests/test_mla_prefill_surface.py; Q_MULT = 1, the data is standard normal)."""
+    q, kv, k_pe, cu_q, cu_k, ref, ref0 = mp.scale_case(causal, scale)
+    diff, need = ml.sees_the_scale(ref, ref0)
+    print("mla prefill scale %.5f causal=%d: |O(scale) - O(SCALE)| = %.3e against 20 x o_bound = %.3e" % (scale, causal, diff, need))
+    assert diff > need
+    got = prefill(q, kv, k_pe, cu_q, cu_k, causal, scale=scale)
+    note("prefill, another scale", check_rows(got, ref, slice(cu_q[0], cu_q[-1]), "mla prefill packed causal=%d scale=%.5f" % (causal, scale)))
+
+
 def test_refusals_on_the_device(built, dev):
     """Contiguity is part of the device check; lse = None leaves o's bits."""
     q, kv, k_pe, cu_q, cu_k = mp.one_case(17, 64, 3)

@@ -112,6 +112,63 @@ def test_decode_several_splits(built, dev, TH, kvs):
     assert bool((bits(got[0][4]) == 0).all()) and bool((got[1][4] == NEG_INF).all())
 
 
+# ---------------------------------------------------------------------------------------------------- 2b. a scale that is not the data's
+
+@pytest.mark.parametrize("kvs", mf.KV_SCALES, ids=["kv2^-8", "kv0.003"])
+@pytest.mark.parametrize("scale", ml.OTHER_SCALES, ids=["yarn", "quarter"])
+@pytest.mark.parametrize("case", ml.SCALE_TH, ids=lambda c: "T%dxHq%d%s" % (c[0], c[1], "-split" if c[2] else ""))
+def test_decode_at_a_scale_that_is_not_the_datas(built, dev, case, scale, kvs):
+    """The one-split case at (3, 5) and the several-splits case at (2, 40) at V3's YaRN scale and at SCALE / 4, at both pool scales, q x Q_MULT:
+    the reference at SCALE is more than 20 x o_bound away (proven without a GPU by tests/test_paged_mla_fp8_surface.py), so a constant in the
+    scale_log2 kv_scale product would show."""
+    T, Hq, split = case
+    q, lens, pool, ref, ref0 = mf.scale_case(T, Hq, split, kvs, scale)
+    S = plan(len(lens), T, Hq, pool)[0]
+    assert (S > 1) == split
+    diff, need = ml.sees_the_scale(ref, ref0)
+    print("mla fp8 scale %.5f kv_scale %g T=%d Hq=%d S=%d: |O(scale) - O(SCALE)| = %.3e against 20 x o_bound = %.3e" % (scale, kvs, T, Hq, S, diff, need))
+    assert diff > need
+    note("decode, another scale", check(*decode(q, pool, lens, kvs, scale=scale), *ref, "mla fp8 scale=%.5f kv_scale=%g S=%d T=%d Hq=%d" % (scale, kvs, S, T, Hq)))
+
+
+def _graph_replays_eager(call, B, T, Hq, need):
+    """call(o, lse, ws) eager, then captured in a graph and replayed on fresh buffers: (eager o, lse on the CPU), bit for bit the replay's."""
+    def buffers():
+        return (torch.full((B, T, Hq, DC), O_FILL, dtype=torch.int16, device="cuda").view(BF),
+                torch.full((B, T, Hq), L_FILL, dtype=torch.int32, device="cuda").view(torch.float32), torch.empty(need, dtype=torch.uint8, device="cuda"))
+
+    eager = buffers()
+    call(*eager)
+    torch.cuda.synchronize()
+    o, lse = eager[0].cpu(), eager[1].cpu()
+    bufs = buffers()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        call(*bufs)
+    torch.cuda.synchronize()
+    assert bool((bits(bufs[0].cpu()) == O_FILL).all())  # captured, not run
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(bits(bufs[0].cpu()), bits(o)) and torch.equal(fbits(bufs[1].cpu()), fbits(lse))
+    return o, lse
+
+
+def test_decode_at_the_yarn_scale_through_a_captured_graph(built, dev):
+    """The several-splits case at (2, 40) at YARN, kv_scale 0.003: the stream kernel and the combine captured and replayed, bit for bit the
+    eager result."""
+    c = pkg()
+    T, Hq, kvs = 2, 40, mf.KV_SCALES[1]
+    q, lens, pool, ref, _ = mf.scale_case(T, Hq, True, kvs, ml.YARN)
+    B = len(lens)
+    S, _, need = plan(B, T, Hq, pool)
+    assert S > 1
+    fixed = (q.to(DEV), pool[0].to(DEV), pool[1].to(DEV), i32(lens), mf.scale_t(kvs).to(DEV))
+    o, lse = _graph_replays_eager(lambda o, lse, ws: c.fa2_decode_paged_mla_bf16_fp8(*fixed, ml.YARN, o, lse, ws), B, T, Hq, need)
+    note("decode, another scale", check(o, lse, *ref, "mla fp8 scale=YARN eager, then a captured graph S=%d" % S))
+
+
 # ---------------------------------------------------------------------------------------------------- 3. bit equality with the bf16 entry
 
 def _bit_cases(T, Hq):

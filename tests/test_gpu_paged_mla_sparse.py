@@ -121,6 +121,60 @@ def test_parity_several_splits(built, dev, TH):
         assert bool((bits(got[0][4]) == 0).all()) and bool((got[1][4] == NEG_INF).all())
 
 
+# ---------------------------------------------------------------------------------------------------- 2b. a scale that is not the data's
+
+@pytest.mark.parametrize("scale", ml.OTHER_SCALES, ids=["yarn", "quarter"])
+@pytest.mark.parametrize("case", ml.SCALE_TH, ids=lambda c: "T%dxHq%d%s" % (c[0], c[1], "-split" if c[2] else ""))
+def test_parity_at_a_scale_that_is_not_the_datas(built, dev, case, scale):
+    """The one-split case at (3, 5), topk 200, and the several-splits case at (2, 40), topk 2048, at V3's YaRN scale and at SCALE / 4,
+    q x Q_MULT: the reference at SCALE is more than 20 x o_bound away (proven without a GPU by tests/test_paged_mla_sparse_surface.py)."""
+    T, Hq, split = case
+    q, lens, pool, idx, ref, ref0 = sp.scale_case(T, Hq, split, scale)
+    S = plan(len(lens), T, Hq, idx.shape[2], pool)[0]
+    assert (S > 1) == split
+    diff, need = ml.sees_the_scale(ref, ref0)
+    print("mla sparse scale %.5f T=%d Hq=%d S=%d: |O(scale) - O(SCALE)| = %.3e against 20 x o_bound = %.3e" % (scale, T, Hq, S, diff, need))
+    assert diff > need
+    note("parity, another scale", check(*sparse(q, pool, lens, idx, scale=scale), *ref, "mla sparse scale=%.5f S=%d T=%d Hq=%d" % (scale, S, T, Hq)))
+
+
+def _graph_replays_eager(call, B, T, Hq, need):
+    """call(o, lse, ws) eager, then captured in a graph and replayed on fresh buffers: (eager o, lse on the CPU), bit for bit the replay's."""
+    def buffers():
+        return (torch.full((B, T, Hq, DC), O_FILL, dtype=torch.int16, device="cuda").view(BF),
+                torch.full((B, T, Hq), L_FILL, dtype=torch.int32, device="cuda").view(torch.float32), torch.empty(need, dtype=torch.uint8, device="cuda"))
+
+    eager = buffers()
+    call(*eager)
+    torch.cuda.synchronize()
+    o, lse = eager[0].cpu(), eager[1].cpu()
+    bufs = buffers()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        call(*bufs)
+    torch.cuda.synchronize()
+    assert bool((bits(bufs[0].cpu()) == O_FILL).all())  # captured, not run
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(bits(bufs[0].cpu()), bits(o)) and torch.equal(fbits(bufs[1].cpu()), fbits(lse))
+    return o, lse
+
+
+def test_parity_at_the_yarn_scale_through_a_captured_graph(built, dev):
+    """The several-splits case at (2, 40) at YARN: the stream kernel and the combine captured and replayed, bit for bit the eager result."""
+    c = pkg()
+    T, Hq = 2, 40
+    q, lens, pool, idx, ref, _ = sp.scale_case(T, Hq, True, ml.YARN)
+    B = len(lens)
+    S, _, need = plan(B, T, Hq, idx.shape[2], pool)
+    assert S > 1
+    fixed = (q.to("cuda"), pool[0].to("cuda"), pool[1].to("cuda"), torch.tensor(lens, dtype=torch.int32, device="cuda"), idx.to("cuda"))
+    o, lse = _graph_replays_eager(lambda o, lse, ws: c.fa2_decode_paged_mla_sparse_bf16(*fixed, ml.YARN, o, lse, ws), B, T, Hq, need)
+    note("parity, another scale", check(o, lse, *ref, "mla sparse scale=YARN eager, then a captured graph S=%d" % S))
+
+
 # ---------------------------------------------------------------------------------------------------- 3. bits of the dense entry
 
 @pytest.mark.parametrize("page", [16, 64])

@@ -348,3 +348,17 @@ def test_merge_and_gather_kernels_resources(tmp_path):
         print(k["name"], {x: k.get(x) for x in ("vgpr", "agpr", "sgpr", "lds", "spill", "sgpr_spill", "scratch")})
         assert k["lds"] == 0 and "v_mfma" not in body and k["vgpr"] <= 128
     assert "v_cvt_pk_bf16_f32" in fs._bodies("attn_merge_states_bf16.hip", tmp_path)[0][1]
+
+
+# ---------------------------------------------------------------------------------------------------- a scale that is not the data's
+
+@pytest.mark.parametrize("scale", mp.OTHER_SCALES, ids=["yarn", "quarter"])
+@pytest.mark.parametrize("causal", [True, False], ids=["causal", "non-causal"])
+def test_the_gpu_cases_at_another_scale_would_notice_the_datas_scale(causal, scale):
+    """tests/test_gpu_mla_prefill.py runs the ragged packed batch at V3's YaRN scale and at SCALE / 4 (Q_MULT = 1: the data is standard
+    normal): a kernel that ran at SCALE whatever it was given would be more than 20 x o_bound from the reference."""
+    assert mp.OTHER_SCALES == ml.OTHER_SCALES and mp.Q_MULT == 1
+    ref, ref0 = mp.scale_case(causal, scale)[5:]
+    diff, need = ml.sees_the_scale(ref, ref0)
+    print("mla prefill scale %.5f causal=%d: |O(scale) - O(SCALE)| = %.3e against 20 x o_bound = %.3e" % (scale, causal, diff, need))
+    assert diff > need

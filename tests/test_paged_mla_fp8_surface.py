@@ -416,3 +416,17 @@ def test_append_and_gather_kernels_resources(tmp_path):
     print(k["name"], _resources(k))
     assert "kv_gather_paged_mla_bf16_fp8_rows" in k["name"] and k["lds"] == 0 and "v_mfma" not in body and k["vgpr"] <= 512
     assert body.count("v_cvt_scalef32_pk_bf16_fp8") == 4 and "v_cvt_pk_bf16_f32" in body
+
+
+# ---------------------------------------------------------------------------------------------------- a scale that is not the data's
+
+@pytest.mark.parametrize("kvs", mf.KV_SCALES, ids=["kv2^-8", "kv0.003"])
+@pytest.mark.parametrize("scale", ml.OTHER_SCALES, ids=["yarn", "quarter"])
+@pytest.mark.parametrize("case", ml.SCALE_TH, ids=lambda c: "T%dxHq%d%s" % (c[0], c[1], "-split" if c[2] else ""))
+def test_the_gpu_cases_at_another_scale_would_notice_the_datas_scale(case, scale, kvs):
+    """tests/test_gpu_paged_mla_fp8.py runs these cases at V3's YaRN scale and at SCALE / 4 with q x Q_MULT: a kernel whose scale_log2 kv_scale
+    product held SCALE whatever it was given would be more than 20 x o_bound from the reference."""
+    ref, ref0 = mf.scale_case(*case, kvs, scale)[3:]
+    diff, need = ml.sees_the_scale(ref, ref0)
+    print("mla fp8 scale %.5f kv_scale %g %s: |O(scale) - O(SCALE)| = %.3e against 20 x o_bound = %.3e" % (scale, kvs, case, diff, need))
+    assert diff > need

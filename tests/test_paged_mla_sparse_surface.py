@@ -331,3 +331,16 @@ def test_kernel_mfmas_are_the_siblings(tmp_path):
     assert fs._loop_mfmas(body) == 4 * (576 // 32) + (512 // 16) * 2 == 136
     assert "ds_read_b64_tr_b16" in body and "v_cvt_pk_bf16_f32" in body and "ds_write_b8" in body
     assert "v_mfma" not in body.replace("v_mfma_f32_16x16x32_bf16", "")
+
+
+# ---------------------------------------------------------------------------------------------------- a scale that is not the data's
+
+@pytest.mark.parametrize("scale", ml.OTHER_SCALES, ids=["yarn", "quarter"])
+@pytest.mark.parametrize("case", ml.SCALE_TH, ids=lambda c: "T%dxHq%d%s" % (c[0], c[1], "-split" if c[2] else ""))
+def test_the_gpu_cases_at_another_scale_would_notice_the_datas_scale(case, scale):
+    """tests/test_gpu_paged_mla_sparse.py runs these cases at V3's YaRN scale and at SCALE / 4 with q x Q_MULT: a kernel that ran at SCALE
+    whatever it was given would be more than 20 x o_bound from the reference."""
+    ref, ref0 = sp.scale_case(*case, scale)[4:]
+    diff, need = ml.sees_the_scale(ref, ref0)
+    print("mla sparse scale %.5f %s: |O(scale) - O(SCALE)| = %.3e against 20 x o_bound = %.3e" % (scale, case, diff, need))
+    assert diff > need

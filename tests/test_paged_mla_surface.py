@@ -323,3 +323,17 @@ def test_append_kernels_resources(tmp_path):
     for k, body in got:
         print(k["name"], {x: k.get(x) for x in ("vgpr", "agpr", "sgpr", "lds", "spill", "sgpr_spill", "scratch")})
         assert "kv_append_paged_mla_bf16_rows" in k["name"] and k["lds"] == 0 and "v_mfma" not in body
+
+
+# ---------------------------------------------------------------------------------------------------- a scale that is not the data's
+
+@pytest.mark.parametrize("scale", ml.OTHER_SCALES, ids=["yarn", "quarter"])
+@pytest.mark.parametrize("case", ml.SCALE_TH, ids=lambda c: "T%dxHq%d%s" % (c[0], c[1], "-split" if c[2] else ""))
+def test_the_gpu_cases_at_another_scale_would_notice_the_datas_scale(case, scale):
+    """tests/test_gpu_paged_mla.py runs these cases at V3's YaRN scale and at SCALE / 4 with q x Q_MULT: a kernel that ran at SCALE whatever it
+    was given would be more than 20 x o_bound from the reference."""
+    assert abs(ml.YARN - 0.1353) < 1e-4 and ml.QUARTER == ml.SCALE / 4 and ml.Q_MULT & (ml.Q_MULT - 1) == 0
+    ref, ref0 = ml.scale_case(*case, scale)[3:]
+    diff, need = ml.sees_the_scale(ref, ref0)
+    print("mla scale %.5f %s: |O(scale) - O(SCALE)| = %.3e against 20 x o_bound = %.3e" % (scale, case, diff, need))
+    assert diff > need
