@@ -538,6 +538,32 @@ def fa2_decode_paged_mla_sparse_bf16_plan(B, T, Hq, topk, max_pages, page):
     return host.fa2_decode_paged_mla_sparse_bf16_plan(B, T, Hq, topk, max_pages, page)
 
 
+def kv_append_paged_index_bf16(k_idx_new, idx_pool, block_table, seqlens, cu_q):
+    """Append the index keys of DeepSeek-V3.2's indexer to their paged cache: k_idx_new bf16 [total_q,128], idx_pool bf16 [P,page,128] behind the
+    block table of the latent cache, the packed convention, seqlens after the append and liveness as in kv_append_paged_mla_bf16; rows copied
+    bit for bit. No rope argument: the model rotates the key, then applies a Hadamard transform, before it caches it. C entry
+    cln_kv_append_paged_index_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.kv_append_paged_index_bf16(k_idx_new, idx_pool, block_table, seqlens, cu_q)
+
+
+def mla_index_logits_paged_bf16(q_idx, weights, idx_pool, block_table, seqlens, logits):
+    """The indexer's logits over the paged index-key cache: q_idx bf16 [B,T,Hi,128], weights fp32 [B,T,Hi], idx_pool bf16 [P,page,128], logits
+    fp32 [B,T,ld]; logits[b,t,j] = sum_h weights[b,t,h] * max(0, q_idx[b,t,h] . k_idx[j]) for 0 <= j < vis(b,t) =
+    clamp(seqlens[b], 0, min(max_pages * page, ld)) - (T - 1 - t), nothing else written or read. Any T >= 1, Hi in 1 … 64. C entry
+    cln_mla_index_logits_paged_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.mla_index_logits_paged_bf16(q_idx, weights, idx_pool, block_table, seqlens, logits)
+
+
+def mla_index_topk(logits, seqlens, topk, indices):
+    """The indexer's exact top-k: logits fp32 [B,T,ld], indices int32 [B,T,topk]; per (b,t) the topk visible positions first under (logit
+    descending, position ascending), written in ascending position order, or the dense list [0 … n-1, -1 …] when n <= topk: the list
+    fa2_decode_paged_mla_sparse_bf16 takes. C entry cln_mla_index_topk (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.mla_index_topk(logits, seqlens, topk, indices)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

@@ -387,4 +387,54 @@ inline int decode_args(const void* const* in, int n_in, const void* const (&out)
   return fa2d::workspace_fits(p, out[2], workspace_bytes) ? CLN_OK : CLN_ERR_BAD_ARG;
 }
 
+// ---------------------------------------------------------------- the DSA indexer (the *_index_* entries)
+// DeepSeek-V3.2's indexer in front of the sparse decode: one pool of index keys [P, page, 128] behind the block table of the latent cache, up
+// to 64 index heads, fp32 logits [B, T, ld] and the exact top-k of a row. Nothing above changes: no existing entry takes these shapes.
+constexpr int kIdxDim = 128, kIdxMaxHeads = 64, kIdxChunk = 1024, kIdxRowsPerWg = kva::kThreads / (kIdxDim / 8);
+constexpr int kTopkThreads = 1024, kTopkBlock = 4 * kTopkThreads;
+// n inputs, all required, 16-byte aligned where al16[i], else 4-byte; the one output with its alignment; the output is no input
+inline int index_args(const void* const* in, const int* al16, int n, const void* out, int out_align) {
+  for (int i = 0; i < n; ++i)
+    if (!in[i] || !cln_aligned(in[i], al16[i] ? 16 : 4)) return CLN_ERR_BAD_ARG;
+  if (!out || !cln_aligned(out, out_align)) return CLN_ERR_BAD_ARG;
+  for (int i = 0; i < n; ++i)
+    if (out == in[i]) return CLN_ERR_BAD_ARG;
+  return CLN_OK;
+}
+// The append of index keys: a thread per 16-byte piece, 16 pieces a row, 16 packed rows a workgroup. -1 for a non-positive dimension, -2 for
+// another page or max_pages page >= 2^31. *wgs = the workgroups.
+inline int index_append_shape(int B, int total_q, int max_pages, int page, int* page_shift, long long* wgs) {
+  if (B <= 0 || total_q <= 0 || max_pages <= 0 || page <= 0) return CLN_ERR_BAD_ARG;
+  fa2d::PagedGeometry g;
+  const int rc = fa2d::paged_geometry(1, 1, max_pages, page, &g);
+  if (rc != CLN_OK) return rc;
+  *page_shift = g.page_shift;
+  *wgs = ((long long)total_q + kIdxRowsPerWg - 1) / kIdxRowsPerWg;
+  return CLN_OK;
+}
+// The logits: a workgroup serves one (sequence, query token, chunk of kIdxChunk keys); the grid is sized from cap = min(max_pages page, ld),
+// the lengths stay on the device. -1 for a non-positive dimension, -2 for Hi > 64, another page, max_pages page >= 2^31, B T >= 2^31 or a
+// grid that does not fit. *cap, *chunks = the chunks of a token, *wgs = B T chunks.
+inline int index_logits_shape(int B, int T, int Hi, long long ld, int max_pages, int page, fa2d::PagedGeometry* g, int* cap, int* chunks,
+                              long long* wgs) {
+  if (B <= 0 || T <= 0 || Hi <= 0 || ld <= 0) return CLN_ERR_BAD_ARG;
+  const int rc = fa2d::paged_geometry(1, 1, max_pages, page, g);
+  if (rc != CLN_OK) return rc;
+  const long long tokens = (long long)B * T;
+  if (Hi > kIdxMaxHeads || tokens > 0x7fffffffLL) return CLN_ERR_UNSUPPORTED;
+  *cap = (int)(g->Nmax < ld ? g->Nmax : ld);
+  *chunks = (*cap + kIdxChunk - 1) / kIdxChunk;
+  *wgs = tokens * *chunks;
+  return *wgs > 0xffffffffLL / fa2d::kThreads ? CLN_ERR_UNSUPPORTED : CLN_OK;
+}
+// The top-k: one workgroup of kTopkThreads per (sequence, query token) row. -1 for a non-positive dimension, -2 for ld >= 2^31, B T >= 2^31,
+// topk B T past 2^61 (the bytes of indices fit a long long) or a grid that does not fit (B T kTopkThreads >= 2^32).
+inline int index_topk_shape(int B, int T, long long ld, int topk, long long* tokens) {
+  if (B <= 0 || T <= 0 || ld <= 0 || topk <= 0) return CLN_ERR_BAD_ARG;
+  *tokens = (long long)B * T;
+  if (ld > 0x7fffffffLL || *tokens > 0x7fffffffLL || *tokens > (1LL << 61) / topk || *tokens > 0xffffffffLL / kTopkThreads)
+    return CLN_ERR_UNSUPPORTED;
+  return CLN_OK;
+}
+
 }  // namespace paged

@@ -1804,3 +1804,96 @@ def fa2_decode_paged_mla_sparse_bf16(q, pool, block_table, seqlens, indices, sof
     rc = fn(q.data_ptr(), pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), indices.data_ptr(), out.data_ptr(), lse_ptr, ws_ptr,
             ws_bytes, B, T, Hq, topk, P, max_pages, page, scale, _stream())
     _raise(name, rc)
+
+
+# ---- the indexer of DeepSeek-V3.2's sparse attention: a paged cache of index keys (128 dims a token) next to the latent cache,
+# behind the same block table; the logits of every visible cache position for a query token; the exact top-k of a row of logits, the list
+# fa2_decode_paged_mla_sparse_bf16 takes
+_IDX_DIM, _IDX_MAX_HEADS = 128, 64
+
+
+def kv_append_paged_index_bf16(k_idx_new, idx_pool, block_table, seqlens, cu_q):
+    """Append the index keys of a packed batch of new tokens to the paged index-key cache; one launch. k_idx_new torch.bfloat16 [total_q,128];
+    idx_pool torch.bfloat16 [P,page,128], written in place, bit for bit; block_table int32 [B,max_pages], seqlens int32 [B] (the lengths AFTER
+    the append), cu_q int32 [B+1]: all as in kv_append_paged_mla_bf16 -- token i of sequence b is packed row cu_q[b] + i and goes to position
+    seqlens[b] - T_b + i, a token that is not live writes nothing, rows of no sequence are untouched. There is no rope argument, on purpose:
+    the model rotates the index key and then applies a Hadamard transform before it caches it, so a rotation fused into this copy would sit
+    in the wrong place. Deterministic. C entry cln_kv_append_paged_index_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "kv_append_paged_index_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_void_p])
+    _decode_check((k_idx_new, idx_pool), (block_table, seqlens, cu_q), torch.bfloat16)
+    if k_idx_new.dim() != 2 or idx_pool.dim() != 3 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    total_q = k_idx_new.shape[0]
+    P, page, _ = idx_pool.shape
+    B, max_pages = block_table.shape
+    _check_shape(k_idx_new, total_q, _IDX_DIM)
+    _check_shape(idx_pool, P, page, _IDX_DIM)
+    _check_shape(seqlens, B)
+    _check_shape(cu_q, B + 1)
+    if page not in _PAGED_PAGES:
+        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+    rc = fn(k_idx_new.data_ptr(), idx_pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), cu_q.data_ptr(), B, total_q, P, max_pages,
+            page, _stream())
+    _raise(name, rc, "%s: max_pages * page too large for one launch" % name)
+
+
+def mla_index_logits_paged_bf16(q_idx, weights, idx_pool, block_table, seqlens, logits):
+    """The logits of DeepSeek-V3.2's indexer over the paged index-key cache; one launch, no workspace. q_idx torch.bfloat16 [B,T,Hi,128];
+    weights fp32 [B,T,Hi] (the caller folds Hi^-1/2, 128^-1/2 and anything else into them); idx_pool torch.bfloat16 [P,page,128];
+    block_table int32 [B,max_pages]; seqlens int32 [B]; logits fp32 [B,T,ld], contiguous, ld >= 1 the caller's. Writes
+    logits[b,t,j] = sum_h weights[b,t,h] * max(0, q_idx[b,t,h] . k_idx[j]) for 0 <= j < vis(b,t) = clamp(seqlens[b], 0, cap) - (T - 1 - t),
+    cap = min(max_pages * page, ld), and nothing else: positions at or past vis keep their bytes, and neither their keys nor their table
+    entries are read. Any T >= 1 (the prompt too), Hi in 1 … 64. fp32 accumulation on the matrix cores, the head sum in a fixed order:
+    deterministic, and a sequence's bits do not depend on its neighbours. C entry cln_mla_index_logits_paged_bf16 (include/cln_amd_ext.h); no
+    CPU path."""
+    name = "mla_index_logits_paged_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 3 + [ctypes.c_longlong] + [ctypes.c_int] * 3 + [ctypes.c_void_p])
+    _decode_check((q_idx, idx_pool), (block_table, seqlens), torch.bfloat16)
+    for t in (weights, logits):
+        _check_dtype(t, torch.float32)
+    _check_dev(weights, logits)
+    if q_idx.dim() != 4 or idx_pool.dim() != 3 or block_table.dim() != 2 or logits.dim() != 3:
+        raise RuntimeError("Tensor size mismatch!")
+    B, T, Hi, D = q_idx.shape
+    P, page, _ = idx_pool.shape
+    ld = logits.shape[2]
+    if D != _IDX_DIM:
+        raise RuntimeError("%s: q_idx of %d dims not supported (%d)" % (name, D, _IDX_DIM))
+    _check_shape(idx_pool, P, page, _IDX_DIM)
+    if block_table.shape[0] != B:
+        raise RuntimeError("Tensor size mismatch!")
+    max_pages = block_table.shape[1]
+    _check_shape(weights, B, T, Hi)
+    _check_shape(seqlens, B)
+    _check_shape(logits, B, T, ld)
+    if Hi > _IDX_MAX_HEADS:
+        raise RuntimeError("%s: %d index heads not supported (1 … %d)" % (name, Hi, _IDX_MAX_HEADS))
+    if page not in _PAGED_PAGES:
+        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+    rc = fn(q_idx.data_ptr(), weights.data_ptr(), idx_pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), logits.data_ptr(), B, T, Hi,
+            ld, P, max_pages, page, _stream())
+    _raise(name, rc, "%s: max_pages * page, B * T or B * T * ceil(cap / 1024) too large for one launch" % name)
+
+
+def mla_index_topk(logits, seqlens, topk, indices):
+    """The exact top-k of DeepSeek-V3.2's indexer; one launch, no workspace. logits fp32 [B,T,ld], contiguous; seqlens int32 [B]; indices int32
+    [B,T,topk], contiguous, every slot written on every call. With n = max(clamp(seqlens[b], 0, ld) - (T - 1 - t), 0): n <= topk gives the
+    dense list [0, …, n - 1, -1, …]; otherwise the topk positions that come first under (logit descending, position ascending), written in
+    ascending position order. Only logits[b,t,0 … n-1] is read. The order is fp32's numeric order with -0 as +0 and ±inf ordinary values; a
+    NaN is ordered by its bit pattern; whatever the values, every index is -1 or a distinct position in [0, n). The list is what
+    fa2_decode_paged_mla_sparse_bf16 takes. Deterministic. C entry cln_mla_index_topk (include/cln_amd_ext.h); no CPU path."""
+    name = "mla_index_topk"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p])
+    _check_dtype(logits, torch.float32)
+    for t in (seqlens, indices):
+        _check_dtype(t, torch.int32)
+    _check_dev(logits, seqlens, indices)
+    if logits.dim() != 3 or indices.dim() != 3:
+        raise RuntimeError("Tensor size mismatch!")
+    B, T, ld = logits.shape
+    topk = int(topk)
+    _check_shape(seqlens, B)
+    _check_shape(indices, B, T, topk)
+    rc = fn(logits.data_ptr(), seqlens.data_ptr(), indices.data_ptr(), B, T, ld, topk, _stream())
+    _raise(name, rc, "%s: ld, B * T or topk * B * T too large for one launch" % name)

@@ -808,3 +808,38 @@ def describe_kv_append_paged_varlen_bf16_fp8(B, total_q, Hq, Hkv, max_pages, pag
     if not isinstance(mode, int):
         raise ValueError("cln_kv_append_paged_varlen_bf16_fp8: rope %r not supported" % (rope_mode,))
     return _describe_bf16("cln_kv_append_paged_varlen_bf16_fp8", tuple(int(x) for x in (B, total_q, Hq, Hkv, max_pages, page, D)) + (mode,))
+
+
+def _describe_index(cname, argtypes, args, size=3072):
+    """The text of an indexer entry's `cname`_describe (ld is a long long there); ValueError for an unsupported or invalid shape."""
+    import ctypes
+    from . import _loader
+    fn = getattr(_loader.load_so("libcln_amd.so"), cname + "_describe")
+    fn.argtypes, fn.restype = list(argtypes) + [ctypes.c_char_p, ctypes.c_int], ctypes.c_int
+    buf = ctypes.create_string_buffer(size)
+    rc = fn(*args, buf, size)
+    if rc < 0:
+        raise ValueError("%s: shape %s not supported (status %d)" % (cname, tuple(args), rc))
+    return buf.value.decode()
+
+
+def describe_kv_append_paged_index_bf16(B, total_q, max_pages, page):
+    """describe() for cln_kv_append_paged_index_bf16 (include/cln_amd_ext.h): the kernel and the launch as text (no GPU needed).
+    ValueError for an unsupported or invalid shape."""
+    return _describe_bf16("cln_kv_append_paged_index_bf16", tuple(int(x) for x in (B, total_q, max_pages, page)), 2048)
+
+
+def describe_mla_index_logits_paged_bf16(B, T, Hi, ld, max_pages, page):
+    """describe() for cln_mla_index_logits_paged_bf16 (include/cln_amd_ext.h): the kernel instantiation, the jobs, the loader, the
+    MFMA count and the order of the head sum as text (no GPU needed). ValueError for an unsupported or invalid shape."""
+    import ctypes
+    i, ll = ctypes.c_int, ctypes.c_longlong
+    return _describe_index("cln_mla_index_logits_paged_bf16", [i, i, i, ll, i, i], tuple(int(x) for x in (B, T, Hi, ld, max_pages, page)))
+
+
+def describe_mla_index_topk(B, T, ld, topk):
+    """describe() for cln_mla_index_topk (include/cln_amd_ext.h): the kernel, the key map, the radix select and the ordered pass
+    as text (no GPU needed). ValueError for an unsupported or invalid shape."""
+    import ctypes
+    i, ll = ctypes.c_int, ctypes.c_longlong
+    return _describe_index("cln_mla_index_topk", [i, i, ll, i], tuple(int(x) for x in (B, T, ld, topk)))

@@ -647,6 +647,44 @@ int cln_fa2_decode_paged_mla_sparse_bf16(const void* q, const void* pool, const 
 int cln_fa2_decode_paged_mla_sparse_bf16_describe(int B, int T, int Hq, int topk, int max_pages, int page, float softmax_scale, char* buf,
                                                   int len);
 
+/* ---- The indexer of DeepSeek-V3.2's sparse attention ("DSA"), bf16: what produces the `indices` of the entry
+ * above. Per layer the model keeps one INDEX KEY of 128 dims per cached token, shared by all index heads: idx_pool bf16 [P,page,128] behind
+ * the block table [B,max_pages] and the lengths [B] of the latent cache. Device pointers are never read by the host; every call is one
+ * launch, deterministic, capturable, without a workspace.
+ *
+ * cln_kv_append_paged_index_bf16: k_idx_new bf16 [total_q,128] packed by cu_q int32 [B+1]; the packed convention, seqlens AFTER the append,
+ * liveness and the caller's contract are cln_kv_append_paged_mla_bf16's: token i of sequence b is packed row cu_q[b] + i at pos =
+ * seqlens[b] - T_b + i, copied bit for bit. No rotation argument, on purpose: the model rotates the key and THEN applies a Hadamard
+ * transform before caching. Status: a missing or misaligned pointer (k_idx_new, idx_pool 16 bytes; the int arrays 4) or idx_pool equal to an
+ * input (-1); P <= 0 (-1); a non-positive B, total_q, max_pages or page (-1); another page or max_pages page >= 2^31 (-2).
+ *
+ * cln_mla_index_logits_paged_bf16: q_idx bf16 [B,T,Hi,128], weights fp32 [B,T,Hi] (the caller folds Hi^-1/2, 128^-1/2 and anything else into
+ * them), logits fp32 [B,T,ld] contiguous, ld >= 1 the caller's. With cap = min(max_pages page, ld) and vis(b,t) = clamp(seqlens[b], 0, cap) -
+ * (T - 1 - t) it writes logits[b,t,j] = sum_h weights[b,t,h] max(0, q_idx[b,t,h] . k_idx[j]) for 0 <= j < vis(b,t) and NOTHING ELSE: a
+ * position at or past vis keeps its bytes, and neither its key nor its table entry is read. Any T >= 1, Hi in 1 ... 64. The products run on
+ * v_mfma_f32_16x16x32_bf16 with fp32 accumulation; ReLU, weight and head sum are fp32 in a fixed order that depends on neither the grid, the
+ * batch nor the length. Inputs whose dot products are finite give no NaN. Status, in this order: a missing or misaligned pointer (q_idx,
+ * idx_pool 16 bytes; weights, block_table, seqlens, logits 4 bytes) or logits equal to an input (-1); P <= 0 (-1); a non-positive B, T, Hi,
+ * ld, max_pages or page (-1); Hi > 64, another page, max_pages page >= 2^31, B T >= 2^31 or a grid that does not fit (-2).
+ *
+ * cln_mla_index_topk: logits as above, indices int32 [B,T,topk] contiguous, any topk >= 1; cap = ld. With n = max(vis(b,t), 0): n <= topk
+ * gives indices[b,t] = [0, 1, ..., n - 1, -1, ..., -1] (the dense list: the sparse decode then gives the dense entry's bits); otherwise the
+ * topk positions that come first under the total order (logit descending, position ascending), WRITTEN IN ASCENDING POSITION ORDER. Every
+ * slot is written on every call; only logits[b,t,0 ... n - 1] is read. The logit order is fp32's numeric order with -0 taken as +0 and +-inf
+ * ordinary values; a NaN is ordered by its bit pattern under the map "sign bit set: complement, else set the sign bit"; whatever the values,
+ * every written index is -1 or a distinct position in [0, n). Status: a missing or misaligned pointer (4 bytes each) or indices equal to an
+ * input (-1); a non-positive B, T, ld or topk (-1); ld >= 2^31, B T >= 2^31, topk B T past 2^61 or a grid that does not fit (B T 1024 >=
+ * 2^32) (-2).
+ */
+int cln_kv_append_paged_index_bf16(const void* k_idx_new, void* idx_pool, const int* block_table, const int* seqlens, const int* cu_q, int B,
+                                   int total_q, int P, int max_pages, int page, void* stream);
+int cln_kv_append_paged_index_bf16_describe(int B, int total_q, int max_pages, int page, char* buf, int len);
+int cln_mla_index_logits_paged_bf16(const void* q_idx, const float* weights, const void* idx_pool, const int* block_table, const int* seqlens,
+                                    float* logits, int B, int T, int Hi, long long ld, int P, int max_pages, int page, void* stream);
+int cln_mla_index_logits_paged_bf16_describe(int B, int T, int Hi, long long ld, int max_pages, int page, char* buf, int len);
+int cln_mla_index_topk(const float* logits, const int* seqlens, int* indices, int B, int T, long long ld, int topk, void* stream);
+int cln_mla_index_topk_describe(int B, int T, long long ld, int topk, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
