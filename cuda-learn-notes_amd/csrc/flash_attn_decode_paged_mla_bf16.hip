@@ -1,7 +1,8 @@
 // Compile unit of the bf16 multi-head latent attention (MLA) decode over a paged latent cache: cln_fa2_decode_paged_mla_bf16_plan /
 // cln_fa2_decode_paged_mla_bf16 / cln_fa2_decode_paged_mla_bf16_describe (include/cln_amd_ext.h; kernel: flash_attn_decode_paged_mla_bf16.cuh;
 // DESIGN 4.4.17). The plan is paged::mla_plan: fa2d::split_plan on B ceil(T Hq / 64) workgroup jobs, the 64-key step and D = 512. The checking
-// order and the status codes are the siblings': the scale first (required, finite, > 0: -1), then the pointers, P, the plan, the workspace.
+// order and the status codes: the scale first (required, finite, > 0: -1), then paged::decode_args with two 16-byte inputs -- the pointers,
+// P, the plan, the workspace.
 #include "flash_attn_decode_paged_mla_bf16.cuh"
 #include "paged_entry.h"
 
@@ -24,24 +25,17 @@ CLN_API int cln_fa2_decode_paged_mla_bf16(const void* q, const void* pool, const
   const void* in[] = {q, pool, block_table, seqlens};  // the last two: 4-byte aligned
   fa2d::PagedGeometry g;
   fa2d::Plan p = {};
-  rc = fa2d::check_pointers(in, 4, 2, {o, lse, workspace});
+  rc = paged::decode_args(in, 4, {o, lse, workspace}, workspace_bytes, P, paged::mla_plan(B, T, Hq, max_pages, page, &g, &p), p, 2);
   if (rc != CLN_OK) return rc;
-  if (P <= 0) return CLN_ERR_BAD_ARG;
-  rc = paged::mla_plan(B, T, Hq, max_pages, page, &g, &p);
-  if (rc != CLN_OK) return rc;
-  if (!fa2d::workspace_fits(p, workspace, workspace_bytes)) return CLN_ERR_BAD_ARG;
   const fa2b::PagedKV kv = {(const bf16_t*)pool, (const bf16_t*)pool, block_table, 1, max_pages, g.page_shift};  // the row is key and value
   return fa2b::launch_decode_paged_mla(q, kv, seqlens, o, lse, workspace, B, T, Hq, p.splits, p.chunk, mult, (hipStream_t)stream);
 }
 
 CLN_API int cln_fa2_decode_paged_mla_bf16_describe(int B, int T, int Hq, int max_pages, int page, float softmax_scale, char* buf, int len) {
-  if (!buf || len <= 0) return CLN_ERR_BAD_ARG;
   float mult = 0.0f;
-  int rc = paged::mla_scale_arg(softmax_scale, &mult);
-  if (rc != CLN_OK) return rc;
   fa2d::PagedGeometry g;
   fa2d::Plan p;
-  rc = paged::mla_plan(B, T, Hq, max_pages, page, &g, &p);
+  const int rc = paged::mla_describe_args(buf, len, softmax_scale, &mult, paged::mla_plan(B, T, Hq, max_pages, page, &g, &p));
   if (rc != CLN_OK) return rc;
   const int R = T * Hq, RG = (R + paged::kMlaRowGroup - 1) / paged::kMlaRowGroup;
   int n = snprintf(buf, len,

@@ -1,9 +1,9 @@
 // Compile unit of the multi-head latent attention (MLA) decode over a paged latent cache held in FP8 (e4m3fn) with bf16 queries:
 // cln_fa2_decode_paged_mla_bf16_fp8_plan / cln_fa2_decode_paged_mla_bf16_fp8 / cln_fa2_decode_paged_mla_bf16_fp8_describe
 // (include/cln_amd_ext.h; kernel: flash_attn_decode_paged_mla_bf16_fp8.cuh). The plan is the bf16 entry's, paged::mla_plan: the
-// key step is still 64 and D still 512. The checking order and the status codes are flash_attn_decode_paged_mla_bf16.hip's: the scale first
-// (required, finite, > 0: -1), then the pointers -- kv_scale among them, behind seqlens: missing, not 4-byte aligned or equal to an output is
-// -1 -- then P, the plan, the workspace.
+// key step is still 64 and D still 512. The checking order and the status codes: the scale first (required, finite, > 0: -1), then
+// paged::decode_args with two 16-byte inputs -- the pointers, kv_scale among them, behind seqlens: missing, not 4-byte aligned or equal to an
+// output is -1 -- then P, the plan, the workspace.
 #include "flash_attn_decode_paged_mla_bf16_fp8.cuh"
 #include "paged_entry.h"
 
@@ -27,24 +27,17 @@ CLN_API int cln_fa2_decode_paged_mla_bf16_fp8(const void* q, const void* pool, c
   const void* in[] = {q, pool, block_table, seqlens, kv_scale};  // the last three: 4-byte aligned
   fa2d::PagedGeometry g;
   fa2d::Plan p = {};
-  rc = fa2d::check_pointers(in, 5, 2, {o, lse, workspace});
+  rc = paged::decode_args(in, 5, {o, lse, workspace}, workspace_bytes, P, paged::mla_plan(B, T, Hq, max_pages, page, &g, &p), p, 2);
   if (rc != CLN_OK) return rc;
-  if (P <= 0) return CLN_ERR_BAD_ARG;
-  rc = paged::mla_plan(B, T, Hq, max_pages, page, &g, &p);
-  if (rc != CLN_OK) return rc;
-  if (!fa2d::workspace_fits(p, workspace, workspace_bytes)) return CLN_ERR_BAD_ARG;
   const fa2b::PagedLatent8 kv = {(const unsigned char*)pool, block_table, max_pages, g.page_shift};  // the row is key and value
   return fa2b::launch_decode_paged_mla_fp8(q, kv, seqlens, kv_scale, o, lse, workspace, B, T, Hq, p.splits, p.chunk, mult, (hipStream_t)stream);
 }
 
 CLN_API int cln_fa2_decode_paged_mla_bf16_fp8_describe(int B, int T, int Hq, int max_pages, int page, float softmax_scale, char* buf, int len) {
-  if (!buf || len <= 0) return CLN_ERR_BAD_ARG;
   float mult = 0.0f;
-  int rc = paged::mla_scale_arg(softmax_scale, &mult);
-  if (rc != CLN_OK) return rc;
   fa2d::PagedGeometry g;
   fa2d::Plan p;
-  rc = paged::mla_plan(B, T, Hq, max_pages, page, &g, &p);
+  const int rc = paged::mla_describe_args(buf, len, softmax_scale, &mult, paged::mla_plan(B, T, Hq, max_pages, page, &g, &p));
   if (rc != CLN_OK) return rc;
   const int R = T * Hq, RG = (R + paged::kMlaRowGroup - 1) / paged::kMlaRowGroup;
   int n = snprintf(buf, len,

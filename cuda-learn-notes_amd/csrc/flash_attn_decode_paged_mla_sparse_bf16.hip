@@ -2,8 +2,8 @@
 // its indexer: cln_fa2_decode_paged_mla_sparse_bf16_plan / cln_fa2_decode_paged_mla_sparse_bf16 / cln_fa2_decode_paged_mla_sparse_bf16_describe
 // (include/cln_amd_ext.h; kernel: flash_attn_decode_paged_mla_sparse_bf16.cuh). The plan is paged::mla_sparse_plan:
 // fa2d::split_plan on B T ceil(Hq / 64) workgroup jobs, the topk index slots in the place of the keys, the 64-slot step and D = 512. The
-// checking order and the status codes are flash_attn_decode_paged_mla_bf16.hip's: the scale first (required, finite, > 0: -1), then the
-// pointers -- indices among the 4-byte aligned int inputs, behind seqlens -- then P, the plan, the workspace.
+// checking order and the status codes: the scale first (required, finite, > 0: -1), then paged::decode_args with two 16-byte inputs -- the
+// pointers, indices among the 4-byte aligned int inputs, behind seqlens -- then P, the plan, the workspace.
 #include "flash_attn_decode_paged_mla_sparse_bf16.cuh"
 #include "paged_entry.h"
 
@@ -27,25 +27,18 @@ CLN_API int cln_fa2_decode_paged_mla_sparse_bf16(const void* q, const void* pool
   const void* in[] = {q, pool, block_table, seqlens, indices};  // the last three: 4-byte aligned
   fa2d::PagedGeometry g;
   fa2d::Plan p = {};
-  rc = fa2d::check_pointers(in, 5, 2, {o, lse, workspace});
+  rc = paged::decode_args(in, 5, {o, lse, workspace}, workspace_bytes, P, paged::mla_sparse_plan(B, T, Hq, topk, max_pages, page, &g, &p), p, 2);
   if (rc != CLN_OK) return rc;
-  if (P <= 0) return CLN_ERR_BAD_ARG;
-  rc = paged::mla_sparse_plan(B, T, Hq, topk, max_pages, page, &g, &p);
-  if (rc != CLN_OK) return rc;
-  if (!fa2d::workspace_fits(p, workspace, workspace_bytes)) return CLN_ERR_BAD_ARG;
   const fa2b::SparseLatent kv = {(const bf16_t*)pool, block_table, indices, max_pages, g.page_shift, topk};  // the row is key and value
   return fa2b::launch_decode_paged_mla_sparse(q, kv, seqlens, o, lse, workspace, B, T, Hq, p.splits, p.chunk, mult, (hipStream_t)stream);
 }
 
 CLN_API int cln_fa2_decode_paged_mla_sparse_bf16_describe(int B, int T, int Hq, int topk, int max_pages, int page, float softmax_scale, char* buf,
                                                           int len) {
-  if (!buf || len <= 0) return CLN_ERR_BAD_ARG;
   float mult = 0.0f;
-  int rc = paged::mla_scale_arg(softmax_scale, &mult);
-  if (rc != CLN_OK) return rc;
   fa2d::PagedGeometry g;
   fa2d::Plan p;
-  rc = paged::mla_sparse_plan(B, T, Hq, topk, max_pages, page, &g, &p);
+  const int rc = paged::mla_describe_args(buf, len, softmax_scale, &mult, paged::mla_sparse_plan(B, T, Hq, topk, max_pages, page, &g, &p));
   if (rc != CLN_OK) return rc;
   const int HG = (Hq + paged::kMlaRowGroup - 1) / paged::kMlaRowGroup;
   int n = snprintf(buf, len,

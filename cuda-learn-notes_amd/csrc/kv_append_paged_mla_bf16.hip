@@ -1,35 +1,17 @@
 // Compile unit of the bf16 packed variable-length append to a paged latent cache (multi-head latent attention): cln_kv_append_paged_mla_bf16 /
-// cln_kv_append_paged_mla_bf16_describe (include/cln_amd_ext.h; kernel: kv_append_paged_mla_bf16.cuh). The checks follow
-// kv_append_paged_varlen_bf16.hip: -1 for a missing, misaligned or aliased pointer, a non-positive dimension, a rotation without a table or
-// max_pos, a table without a rotation, q without q_out; -2 for another page, rope_mode, max_pages page >= 2^31 or a grid that does not fit.
-// Unlike there, rope_mode 0 takes q and q_out: the query rows are then copied bit for bit.
+// cln_kv_append_paged_mla_bf16_describe (include/cln_amd_ext.h; kernel: kv_append_paged_mla_bf16.cuh). The checks are
+// paged::mla_append_args, then paged::mla_append_shape: -1 for a missing, misaligned or aliased pointer, a non-positive dimension, a rotation
+// without a table or max_pos, a table without a rotation, q without q_out; -2 for another page, rope_mode, max_pages page >= 2^31 or a grid
+// that does not fit. Unlike kv_append_paged_varlen_bf16.hip, rope_mode 0 takes q and q_out: the query rows are then copied bit for bit.
 #include "kv_append_paged_mla_bf16.cuh"
 #include "paged_entry.h"
 
 static_assert(kva::kMlaDc == paged::kMlaDc && kva::kMlaDr == paged::kMlaDr, "paged::mla_append_shape counts this kernel's pieces");
 
-namespace {
-int mla_append_args(const void* c_new, const void* k_pe_new, const void* pool, const int* block_table, const int* seqlens, const int* cu_q,
-                    const void* q, const void* q_out, const float* rope_table, int P, int max_pos, int rope_mode) {
-  if (!c_new || !k_pe_new || !pool || !block_table || !seqlens || !cu_q) return CLN_ERR_BAD_ARG;
-  if (!cln_aligned16(c_new) || !cln_aligned16(k_pe_new) || !cln_aligned16(pool) || !cln_aligned16(q) || !cln_aligned16(q_out))
-    return CLN_ERR_BAD_ARG;
-  if (!cln_aligned(block_table, 4) || !cln_aligned(seqlens, 4) || !cln_aligned(cu_q, 4) || !cln_aligned(rope_table, 4)) return CLN_ERR_BAD_ARG;
-  const void* const in[] = {c_new, k_pe_new, block_table, seqlens, cu_q, rope_table};
-  for (const void* p : in)
-    if (p && (p == pool || p == q_out)) return CLN_ERR_BAD_ARG;  // no output is an input; q_out may be q
-  if (pool == q || pool == q_out) return CLN_ERR_BAD_ARG;
-  if (P <= 0 || (q == nullptr) != (q_out == nullptr)) return CLN_ERR_BAD_ARG;
-  if (rope_mode == 0 && rope_table) return CLN_ERR_BAD_ARG;
-  if ((rope_mode == 1 || rope_mode == 2) && (!rope_table || max_pos <= 0)) return CLN_ERR_BAD_ARG;
-  return CLN_OK;
-}
-}  // namespace
-
 CLN_API int cln_kv_append_paged_mla_bf16(const void* c_new, const void* k_pe_new, void* pool, const int* block_table, const int* seqlens,
                                          const int* cu_q, const void* q, void* q_out, const float* rope_table, int B, int total_q, int Hq, int P,
                                          int max_pages, int page, int max_pos, int rope_mode, void* stream) {
-  int rc = mla_append_args(c_new, k_pe_new, pool, block_table, seqlens, cu_q, q, q_out, rope_table, P, max_pos, rope_mode);
+  int rc = paged::mla_append_args(c_new, k_pe_new, pool, block_table, seqlens, cu_q, nullptr, false, q, q_out, rope_table, P, max_pos, rope_mode);
   if (rc != CLN_OK) return rc;
   int page_shift = 0;
   long long y = 0;

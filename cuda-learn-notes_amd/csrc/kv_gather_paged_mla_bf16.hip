@@ -1,22 +1,17 @@
 // Compile unit of the bf16 packed gather out of a paged latent cache (multi-head latent attention): cln_kv_gather_paged_mla_bf16 /
-// cln_kv_gather_paged_mla_bf16_describe (include/cln_amd_ext.h; kernel: kv_gather_paged_mla_bf16.cuh). The checks follow
-// kv_append_paged_mla_bf16.hip: -1 for a missing, misaligned or aliased pointer (starts may be null) or a non-positive dimension; -2 for
+// cln_kv_gather_paged_mla_bf16_describe (include/cln_amd_ext.h; kernel: kv_gather_paged_mla_bf16.cuh). The checks are
+// paged::mla_gather_args, then paged::mla_gather_shape: -1 for a missing, misaligned or aliased pointer (starts may be null) or a non-positive dimension; -2 for
 // another page, max_pages page >= 2^31 or a grid that does not fit.
 #include "kv_gather_paged_mla_bf16.cuh"
 #include "paged_entry.h"
 
 CLN_API int cln_kv_gather_paged_mla_bf16(const void* pool, const int* block_table, const int* starts, const int* cu_k, void* out, int B,
                                          int total_k, int P, int max_pages, int page, void* stream) {
-  if (!pool || !block_table || !cu_k || !out) return CLN_ERR_BAD_ARG;
-  if (!cln_aligned16(pool) || !cln_aligned16(out) || !cln_aligned(block_table, 4) || !cln_aligned(starts, 4) || !cln_aligned(cu_k, 4))
-    return CLN_ERR_BAD_ARG;
-  const void* const in[] = {pool, block_table, starts, cu_k};
-  for (const void* p : in)
-    if (p == out) return CLN_ERR_BAD_ARG;  // the output is no input
-  if (P <= 0) return CLN_ERR_BAD_ARG;
+  int rc = paged::mla_gather_args(pool, block_table, starts, cu_k, nullptr, false, out, P);
+  if (rc != CLN_OK) return rc;
   int page_shift = 0;
   long long y = 0;
-  const int rc = paged::mla_gather_shape(B, total_k, max_pages, page, &page_shift, &y);
+  rc = paged::mla_gather_shape(B, total_k, max_pages, page, &page_shift, &y);
   if (rc != CLN_OK) return rc;
   const kva::ArgsMlaGatherBf16 a = {(const bf16_t*)pool, block_table, starts, cu_k, (bf16_t*)out, B, total_k, P, max_pages, page_shift};
   return kva::launch_mla_gather_bf16(a, y, (hipStream_t)stream);

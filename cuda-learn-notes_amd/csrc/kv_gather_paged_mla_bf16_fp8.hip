@@ -1,6 +1,6 @@
 // Compile unit of the packed gather out of a paged latent cache held in FP8 into bf16 rows (multi-head latent attention):
 // cln_kv_gather_paged_mla_bf16_fp8 / cln_kv_gather_paged_mla_bf16_fp8_describe (include/cln_amd_ext.h; kernel: kv_gather_paged_mla_bf16_fp8.cuh;
-// DESIGN 4.4.19). The checks are kv_gather_paged_mla_bf16.hip's, in its order, with kv_scale (fp32 [1] on the device) behind cu_k: -1 for a
+// DESIGN 4.4.19). The checks are paged::mla_gather_args with kv_scale (fp32 [1] on the device, behind cu_k) required, then paged::mla_gather_shape: -1 for a
 // missing, misaligned or aliased pointer (starts may be null) or a non-positive dimension; -2 for another page, max_pages page >= 2^31 or a grid
 // that does not fit.
 #include "kv_gather_paged_mla_bf16_fp8.cuh"
@@ -8,17 +8,11 @@
 
 CLN_API int cln_kv_gather_paged_mla_bf16_fp8(const void* pool, const int* block_table, const int* starts, const int* cu_k, const float* kv_scale,
                                              void* out, int B, int total_k, int P, int max_pages, int page, void* stream) {
-  if (!pool || !block_table || !cu_k || !kv_scale || !out) return CLN_ERR_BAD_ARG;
-  if (!cln_aligned16(pool) || !cln_aligned16(out) || !cln_aligned(block_table, 4) || !cln_aligned(starts, 4) || !cln_aligned(cu_k, 4) ||
-      !cln_aligned(kv_scale, 4))
-    return CLN_ERR_BAD_ARG;
-  const void* const in[] = {pool, block_table, starts, cu_k, kv_scale};
-  for (const void* p : in)
-    if (p == out) return CLN_ERR_BAD_ARG;  // the output is no input
-  if (P <= 0) return CLN_ERR_BAD_ARG;
+  int rc = paged::mla_gather_args(pool, block_table, starts, cu_k, kv_scale, true, out, P);
+  if (rc != CLN_OK) return rc;
   int page_shift = 0;
   long long y = 0;
-  const int rc = paged::mla_gather_shape(B, total_k, max_pages, page, &page_shift, &y);
+  rc = paged::mla_gather_shape(B, total_k, max_pages, page, &page_shift, &y);
   if (rc != CLN_OK) return rc;
   const kva::ArgsMlaGatherBf16Fp8 a = {(const uint8_t*)pool, block_table, starts, cu_k, kv_scale, (bf16_t*)out, B, total_k, P, max_pages, page_shift};
   return kva::launch_mla_gather_bf16_fp8(a, y, (hipStream_t)stream);

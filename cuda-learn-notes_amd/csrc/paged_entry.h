@@ -324,6 +324,34 @@ inline int mla_sparse_plan(int B, int T, int Hq, int topk, int max_pages, int pa
   if (Hq > kMlaMaxHq || tokens > 0x7fffffffLL) return CLN_ERR_UNSUPPORTED;
   return fa2d::split_plan(tokens * ((Hq + kMlaRowGroup - 1) / kMlaRowGroup), tokens * Hq, topk, kMlaKeyStep, kMlaDc, p);
 }
+// The prologue of the three decode describes in the order of its status codes: the buffer, the scale (*mult as above), the entry's plan.
+inline int mla_describe_args(const char* buf, int len, float softmax_scale, float* mult, int plan_rc) {
+  if (!buf || len <= 0) return CLN_ERR_BAD_ARG;
+  const int rc = mla_scale_arg(softmax_scale, mult);
+  return rc != CLN_OK ? rc : plan_rc;
+}
+// The pointers of the two appends and what goes with them, all -1: c_new, k_pe_new, pool, q and q_out 16-byte aligned, the int32 arrays,
+// kv_scale and rope_table 4-byte; q, q_out and rope_table may be null, kv_scale is required only where fp8 (the bf16 entry passes null). No
+// output (pool, q_out) is an input or the other output, but q_out may be q: a thread reads its pairs before it writes. append_args does not
+// serve: there is one pool, and unlike there rope_mode 0 takes q with q_out (the query rows are then copied bit for bit); a table goes with a
+// rotation and max_pos > 0, never with rope_mode 0.
+inline int mla_append_args(const void* c_new, const void* k_pe_new, const void* pool, const int* block_table, const int* seqlens, const int* cu_q,
+                           const float* kv_scale, bool fp8, const void* q, const void* q_out, const float* rope_table, int P, int max_pos,
+                           int rope_mode) {
+  if (!c_new || !k_pe_new || !pool || !block_table || !seqlens || !cu_q || (fp8 && !kv_scale)) return CLN_ERR_BAD_ARG;
+  if (!cln_aligned16(c_new) || !cln_aligned16(k_pe_new) || !cln_aligned16(pool) || !cln_aligned16(q) || !cln_aligned16(q_out))
+    return CLN_ERR_BAD_ARG;
+  if (!cln_aligned(block_table, 4) || !cln_aligned(seqlens, 4) || !cln_aligned(cu_q, 4) || !cln_aligned(kv_scale, 4) || !cln_aligned(rope_table, 4))
+    return CLN_ERR_BAD_ARG;
+  const void* const in[] = {c_new, k_pe_new, block_table, seqlens, cu_q, kv_scale, rope_table};
+  for (const void* p : in)
+    if (p && (p == pool || p == q_out)) return CLN_ERR_BAD_ARG;
+  if (pool == q || pool == q_out) return CLN_ERR_BAD_ARG;
+  if (P <= 0 || (q == nullptr) != (q_out == nullptr)) return CLN_ERR_BAD_ARG;
+  if (rope_mode == 0 && rope_table) return CLN_ERR_BAD_ARG;
+  if ((rope_mode == 1 || rope_mode == 2) && (!rope_table || max_pos <= 0)) return CLN_ERR_BAD_ARG;
+  return CLN_OK;
+}
 // The append: a thread per 16-byte piece; per token one pool row and, with q, Hq query rows of 64 copied pieces and the rotary pieces (4 with
 // the half-split pairs, which a thread moves two at a time, else 8). *y = the workgroups per token.
 inline int mla_append_pieces(int rope_mode) { return kMlaDc / 8 + (rope_mode == 1 ? kMlaDr / 16 : kMlaDr / 8); }
@@ -375,12 +403,26 @@ inline int merge_shape(long long rows, int D, int* rows_per_wg, long long* wgs) 
 inline int mla_gather_shape(int B, int total_k, int max_pages, int page, int* page_shift, long long* y) {
   return mla_append_shape(B, total_k, 1, max_pages, page, 0, false, page_shift, y);
 }
+// The pointers of the two gathers, all -1: pool and out 16-byte aligned, block_table, starts, cu_k and kv_scale 4-byte; starts may be null,
+// kv_scale is required only where fp8 (the bf16 entry passes null); the output is no input. Then P.
+inline int mla_gather_args(const void* pool, const int* block_table, const int* starts, const int* cu_k, const float* kv_scale, bool fp8,
+                           const void* out, int P) {
+  if (!pool || !block_table || !cu_k || (fp8 && !kv_scale) || !out) return CLN_ERR_BAD_ARG;
+  if (!cln_aligned16(pool) || !cln_aligned16(out) || !cln_aligned(block_table, 4) || !cln_aligned(starts, 4) || !cln_aligned(cu_k, 4) ||
+      !cln_aligned(kv_scale, 4))
+    return CLN_ERR_BAD_ARG;
+  const void* const in[] = {pool, block_table, starts, cu_k, kv_scale};
+  for (const void* p : in)
+    if (p == out) return CLN_ERR_BAD_ARG;
+  return P <= 0 ? CLN_ERR_BAD_ARG : CLN_OK;
+}
 
 // The arguments of a decode entry in the order of their status codes: the pointers (fa2d::check_pointers), P, the status of the entry's plan
-// and, where the plan splits the keys, the workspace. The *_sink_* entries put their fp32 sinks [Hq] last in `in`, behind seqlens.
+// and, where the plan splits the keys, the workspace. The *_sink_* entries put their fp32 sinks [Hq] last in `in`, behind seqlens. first_int =
+// the leading inputs that are 16-byte aligned: q and the two pools, or for the MLA entries, which have one pool, 2.
 inline int decode_args(const void* const* in, int n_in, const void* const (&out)[3], long long workspace_bytes, int P, int plan_rc,
-                       const fa2d::Plan& p) {
-  const int rc = fa2d::check_pointers(in, n_in, 3, out);
+                       const fa2d::Plan& p, int first_int = 3) {
+  const int rc = fa2d::check_pointers(in, n_in, first_int, out);
   if (rc != CLN_OK) return rc;
   if (P <= 0) return CLN_ERR_BAD_ARG;
   if (plan_rc != CLN_OK) return plan_rc;

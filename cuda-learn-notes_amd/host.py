@@ -750,6 +750,10 @@ def _paged_headdim_error(name, D, head_dims):
     return RuntimeError("%s: head dim %d not supported (%s)" % (name, D, " or ".join(map(str, head_dims))))
 
 
+def _paged_page_error(name, page):
+    return RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+
+
 def _paged_groups(name):
     """The group sizes Hq / Hkv the paged attention entry `name` takes."""
     return _PAGED_GROUPS_ANYG if "_anyg_" in name else _PAGED_GROUPS
@@ -763,7 +767,7 @@ def _paged_unsupported(name, B, Hq, Hkv, max_pages, page, D, head_dims=_HEAD_DIM
         return RuntimeError("%s: group size %d (= Hq %d / Hkv %d) not supported (%s)"
                             % (name, Hq // Hkv, Hq, Hkv, "1 … 16" if "_anyg_" in name else "1, 2, 4 or 8"))
     if page not in _PAGED_PAGES:
-        return RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+        return _paged_page_error(name, page)
     return RuntimeError("%s: max_pages * page or B * Hkv * splits too large for one launch" % name)
 
 
@@ -876,6 +880,18 @@ def _paged_attention(name, dtype, q_dims, plan, q, k_pages, v_pages, block_table
     _raise(name, rc, too_large)
 
 
+def _rope_table_max_pos(rope_table, D):
+    """The max_pos of the optional fp32 rope_table [max_pos, D] of an append entry; 0 without one."""
+    if rope_table is None:
+        return 0
+    _check_dtype(rope_table, torch.float32)
+    _check_dev(rope_table)
+    if rope_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    _check_shape(rope_table, rope_table.shape[0], D)
+    return rope_table.shape[0]
+
+
 def _kv_append_paged(name, dtype, k_new, v_new, k_pages, v_pages, block_table, seqlens, cu_q, k_scale, v_scale, q, q_out, rope_table, rope,
                      head_dims=_HEAD_DIMS):
     """The body of every append entry. k_new, v_new: dtype [B,T,Hkv,D], or with cu_q the packed [total_q,Hkv,D]; q, q_out alike with Hq heads;
@@ -909,24 +925,18 @@ def _kv_append_paged(name, dtype, k_new, v_new, k_pages, v_pages, block_table, s
     _check_shape(seqlens, B)
     if packed:
         _check_shape(cu_q, B + 1)
-    Hq, max_pos = Hkv, 0
+    Hq = Hkv
     if q is not None:
         if q.dim() != k_new.dim():
             raise RuntimeError("Tensor size mismatch!")
         Hq = q.shape[-2]
         _check_shape(q, *lead, Hq, D)
         _check_shape(q_out, *lead, Hq, D)
-    if rope_table is not None:
-        _check_dtype(rope_table, torch.float32)
-        _check_dev(rope_table)
-        if rope_table.dim() != 2:
-            raise RuntimeError("Tensor size mismatch!")
-        max_pos = rope_table.shape[0]
-        _check_shape(rope_table, max_pos, D)
+    max_pos = _rope_table_max_pos(rope_table, D)
     if D not in head_dims:
         raise _paged_headdim_error(name, D, head_dims)
     if page not in _PAGED_PAGES:
-        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+        raise _paged_page_error(name, page)
     if Hq % Hkv:
         raise RuntimeError("%s: %d query heads are no multiple of %d KV heads" % (name, Hq, Hkv))
     ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
@@ -1398,23 +1408,159 @@ def fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16(q, k_pages, v_page
 _MLA_DC, _MLA_DR, _MLA_DK, _MLA_MAX_HQ = 512, 64, 576, 128
 
 
+def _softmax_scale(name, softmax_scale):
+    """The float of the softmax scale of the MLA entries, which has no default."""
+    scale = float(softmax_scale)
+    if not (0.0 < scale < math.inf):
+        raise RuntimeError("%s: softmax_scale %r not supported (finite and > 0; there is no default)" % (name, softmax_scale))
+    return scale
+
+
+def _mla_fp8_check(name, pool, kv_scale):
+    """What the MLA FP8 entries ask of the pool and its scale: a torch.float8_e4m3fn pool of three dims and an fp32 [1] scale on the GPU."""
+    _check_dtype(pool, torch.float8_e4m3fn)
+    _check_dtype(kv_scale, torch.float32)
+    _check_dev(pool, kv_scale)
+    _check_shape(kv_scale, 1)
+    if pool.dim() != 3:
+        raise RuntimeError("Tensor size mismatch!")
+
+
+def _mla_plan(name, dims, max_t, too_large):
+    """The body of the MLA *_plan wrappers: the C entry cln_<name>_plan for dims = (B, T, Hq, …, max_pages, page) and its error texts. max_t
+    (the T the entry takes at most, None for no cap) and too_large (what its last -2 says) are the entry's: they choose the text of a -2,
+    never the status."""
+    dims = tuple(map(int, dims))
+    rc, plan = _decode_plan("cln_%s_plan" % name, dims)
+    if rc == -2:
+        T, Hq, page = dims[1], dims[2], dims[-1]
+        if max_t is not None and T > max_t:
+            raise RuntimeError("%s: T %d not supported (1 … %d)" % (name, T, max_t))
+        if Hq > _MLA_MAX_HQ:
+            raise RuntimeError("%s: %d query heads not supported (1 … %d)" % (name, Hq, _MLA_MAX_HQ))
+        if page not in _PAGED_PAGES:
+            raise _paged_page_error(name, page)
+        raise RuntimeError(too_large % name)
+    _raise(name, rc)
+    return plan
+
+
+def _mla_decode(name, plan, q, pool, block_table, seqlens, kv_scale, indices, softmax_scale, out, lse, workspace):
+    """The body of every MLA decode entry over the paged latent cache. q: bf16 [B,T,Hq,576], out: bf16 [B,T,Hq,512]; the pool holds bf16, or
+    for a *_fp8 entry e4m3 with kv_scale: one more input pointer behind seqlens; indices = the int32 [B,T,topk] of a *_sparse_* entry: one
+    more input pointer there and topk behind Hq, for the entry and its plan. plan = the entry's *_plan. What an entry takes is read from its
+    name, not from an argument being None: a forgotten tensor must not select another C prototype."""
+    fp8, sparse = name.endswith("_fp8"), "_sparse_" in name
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * (7 + fp8 + sparse) + [ctypes.c_longlong] + [ctypes.c_int] * (6 + sparse)
+                 + [ctypes.c_float, ctypes.c_void_p])
+    scale = _softmax_scale(name, softmax_scale)
+    _decode_check((q, out) if fp8 else (q, pool, out), (block_table, seqlens, indices) if sparse else (block_table, seqlens), torch.bfloat16)
+    if fp8:
+        _mla_fp8_check(name, pool, kv_scale)
+    if q.dim() != 4 or pool.dim() != 3 or block_table.dim() != 2 or (sparse and indices.dim() != 3):
+        raise RuntimeError("Tensor size mismatch!")
+    B, T, Hq, Dk = q.shape
+    P, page, _ = pool.shape
+    if Dk != _MLA_DK:
+        raise RuntimeError("%s: q of %d dims not supported (%d = 512 latent + 64 rotary)" % (name, Dk, _MLA_DK))
+    _check_shape(pool, P, page, _MLA_DK)
+    if block_table.shape[0] != B:
+        raise RuntimeError("Tensor size mismatch!")
+    max_pages = block_table.shape[1]
+    _check_shape(out, B, T, Hq, _MLA_DC)
+    _check_shape(seqlens, B)
+    topk = ()
+    if sparse:
+        topk = (indices.shape[2],)
+        _check_shape(indices, B, T, *topk)
+        if not indices.is_contiguous():
+            raise RuntimeError("%s: indices must be contiguous [B,T,topk]" % name)
+    lse_ptr = _decode_lse(lse, B, T, Hq)
+    ws_ptr, ws_bytes = _decode_workspace(name, plan(B, T, Hq, *topk, max_pages, page)[2], workspace, q.device)
+    more = ((kv_scale.data_ptr(),) if fp8 else ()) + ((indices.data_ptr(),) if sparse else ())
+    rc = fn(q.data_ptr(), pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), *more, out.data_ptr(), lse_ptr, ws_ptr, ws_bytes, B, T,
+            Hq, *topk, P, max_pages, page, scale, _stream())
+    _raise(name, rc)
+
+
+def _mla_append(name, c_new, k_pe_new, pool, block_table, seqlens, cu_q, kv_scale, q, q_out, rope_table, rope):
+    """The body of the two appends to the paged latent cache. c_new: bf16 [total_q,512], k_pe_new: bf16 [total_q,64], q, q_out: bf16
+    [total_q,Hq,576]; the pool holds bf16, or for the *_fp8 entry e4m3 with kv_scale: one more input pointer behind cu_q. Unlike the GQA
+    appends, rope "none" takes q and q_out."""
+    fp8 = name.endswith("_fp8")
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * (9 + fp8) + [ctypes.c_int] * 8 + [ctypes.c_void_p])
+    if rope not in _ROPE_MODES:
+        raise RuntimeError("%s: rope %r not supported ('none', 'half' or 'interleaved')" % (name, rope))
+    mode = _ROPE_MODES[rope]
+    if mode == 0 and rope_table is not None:
+        raise RuntimeError("%s: rope 'none' takes no rope_table" % name)
+    if mode != 0 and rope_table is None:
+        raise RuntimeError("%s: rope %r needs a rope_table (kv_append_rope_table(max_pos, 64))" % (name, rope))
+    if (q is None) != (q_out is None):
+        raise RuntimeError("%s: q and q_out are given together or not at all" % name)
+    rows = (c_new, k_pe_new) if fp8 else (c_new, k_pe_new, pool)
+    _decode_check(rows + (q, q_out) if q is not None else rows, (block_table, seqlens, cu_q), torch.bfloat16)
+    if fp8:
+        _mla_fp8_check(name, pool, kv_scale)
+    if c_new.dim() != 2 or k_pe_new.dim() != 2 or pool.dim() != 3 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    total_q = c_new.shape[0]
+    P, page, _ = pool.shape
+    B, max_pages = block_table.shape
+    _check_shape(c_new, total_q, _MLA_DC)
+    _check_shape(k_pe_new, total_q, _MLA_DR)
+    _check_shape(pool, P, page, _MLA_DK)
+    _check_shape(seqlens, B)
+    _check_shape(cu_q, B + 1)
+    Hq = 1
+    if q is not None:
+        if q.dim() != 3:
+            raise RuntimeError("Tensor size mismatch!")
+        Hq = q.shape[1]
+        _check_shape(q, total_q, Hq, _MLA_DK)
+        _check_shape(q_out, total_q, Hq, _MLA_DK)
+    max_pos = _rope_table_max_pos(rope_table, _MLA_DR)
+    if page not in _PAGED_PAGES:
+        raise _paged_page_error(name, page)
+    rc = fn(c_new.data_ptr(), k_pe_new.data_ptr(), pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), cu_q.data_ptr(),
+            *((kv_scale.data_ptr(),) if fp8 else ()), None if q is None else q.data_ptr(), None if q is None else q_out.data_ptr(),
+            None if rope_table is None else rope_table.data_ptr(), B, total_q, Hq, P, max_pages, page, max_pos, mode, _stream())
+    _raise(name, rc, "%s: max_pages * page or total_q too large for one launch" % name)
+
+
+def _mla_gather(name, pool, block_table, cu_k, kv_scale, out, starts):
+    """The body of the two gathers out of the paged latent cache into out: bf16 [total_k,576]; the pool holds bf16, or for the *_fp8 entry e4m3 with
+    kv_scale: one more input pointer behind cu_k."""
+    fp8 = name.endswith("_fp8")
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * (5 + fp8) + [ctypes.c_int] * 5 + [ctypes.c_void_p])
+    _decode_check((out,) if fp8 else (pool, out), (block_table, cu_k) + (() if starts is None else (starts,)), torch.bfloat16)
+    if fp8:
+        _mla_fp8_check(name, pool, kv_scale)
+    if pool.dim() != 3 or block_table.dim() != 2 or out.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    P, page, _ = pool.shape
+    B, max_pages = block_table.shape
+    total_k = out.shape[0]
+    _check_shape(pool, P, page, _MLA_DK)
+    _check_shape(out, total_k, _MLA_DK)
+    _check_shape(cu_k, B + 1)
+    if starts is not None:
+        _check_shape(starts, B)
+    if page not in _PAGED_PAGES:
+        raise _paged_page_error(name, page)
+    rc = fn(pool.data_ptr(), block_table.data_ptr(), None if starts is None else starts.data_ptr(), cu_k.data_ptr(),
+            *((kv_scale.data_ptr(),) if fp8 else ()), out.data_ptr(), B, total_k, P, max_pages, page, _stream())
+    _raise(name, rc, "%s: max_pages * page or total_k too large for one launch" % name)
+
+
+_MLA_DECODE_TOO_LARGE ="%s: max_pages * page or B * ceil(T * Hq / 64) * splits too large for one launch"
+
+
 def fa2_decode_paged_mla_bf16_plan(B, T, Hq, max_pages, page):
     """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_bf16: fa2d::split_plan on B * ceil(T * Hq / 64) workgroup jobs (a row group of
     64 query rows each), in units of max(page, 64) keys, at D = 512; a function of these five numbers only (cln_fa2_decode_paged_mla_bf16_plan,
     include/cln_amd_ext.h). T in 1 … 8, Hq in 1 … 128. No GPU needed."""
-    name = "fa2_decode_paged_mla_bf16"
-    B, T, Hq, max_pages, page = (int(x) for x in (B, T, Hq, max_pages, page))
-    rc, plan = _decode_plan("cln_%s_plan" % name, (B, T, Hq, max_pages, page))
-    if rc == -2:
-        if T > 8:
-            raise RuntimeError("%s: T %d not supported (1 … 8)" % (name, T))
-        if Hq > _MLA_MAX_HQ:
-            raise RuntimeError("%s: %d query heads not supported (1 … %d)" % (name, Hq, _MLA_MAX_HQ))
-        if page not in _PAGED_PAGES:
-            raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
-        raise RuntimeError("%s: max_pages * page or B * ceil(T * Hq / 64) * splits too large for one launch" % name)
-    _raise(name, rc)
-    return plan
+    return _mla_plan("fa2_decode_paged_mla_bf16", (B, T, Hq, max_pages, page), 8, _MLA_DECODE_TOO_LARGE)
 
 
 def fa2_decode_paged_mla_bf16(q, pool, block_table, seqlens, softmax_scale, out, lse=None, workspace=None):
@@ -1427,29 +1573,8 @@ def fa2_decode_paged_mla_bf16(q, pool, block_table, seqlens, softmax_scale, out,
     192 ** -0.5 * mscale ** 2, not 576 ** -0.5). T in 1 … 8, Hq in 1 … 128, page in {16, 32, 64, 128, 256}. workspace: any contiguous GPU tensor
     of at least fa2_decode_paged_mla_bf16_plan(...)[2] bytes; allocated here on the current stream when None and the plan splits the keys.
     Deterministic. C entry cln_fa2_decode_paged_mla_bf16 (include/cln_amd_ext.h); no CPU path."""
-    name = "fa2_decode_paged_mla_bf16"
-    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 7 + [ctypes.c_longlong] + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_void_p])
-    scale = float(softmax_scale)
-    if not (0.0 < scale < math.inf):
-        raise RuntimeError("%s: softmax_scale %r not supported (finite and > 0; there is no default)" % (name, softmax_scale))
-    _decode_check((q, pool, out), (block_table, seqlens), torch.bfloat16)
-    if q.dim() != 4 or pool.dim() != 3 or block_table.dim() != 2:
-        raise RuntimeError("Tensor size mismatch!")
-    B, T, Hq, Dk = q.shape
-    P, page, _ = pool.shape
-    if Dk != _MLA_DK:
-        raise RuntimeError("%s: q of %d dims not supported (%d = 512 latent + 64 rotary)" % (name, Dk, _MLA_DK))
-    _check_shape(pool, P, page, _MLA_DK)
-    if block_table.shape[0] != B:
-        raise RuntimeError("Tensor size mismatch!")
-    max_pages = block_table.shape[1]
-    _check_shape(out, B, T, Hq, _MLA_DC)
-    _check_shape(seqlens, B)
-    lse_ptr = _decode_lse(lse, B, T, Hq)
-    ws_ptr, ws_bytes = _decode_workspace(name, fa2_decode_paged_mla_bf16_plan(B, T, Hq, max_pages, page)[2], workspace, q.device)
-    rc = fn(q.data_ptr(), pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), out.data_ptr(), lse_ptr, ws_ptr, ws_bytes, B, T, Hq, P,
-            max_pages, page, scale, _stream())
-    _raise(name, rc)
+    _mla_decode("fa2_decode_paged_mla_bf16", fa2_decode_paged_mla_bf16_plan, q, pool, block_table, seqlens, None, None, softmax_scale, out, lse,
+                workspace)
 
 
 def kv_append_paged_mla_bf16(c_new, k_pe_new, pool, block_table, seqlens, cu_q, q=None, q_out=None, rope_table=None, rope="none"):
@@ -1462,48 +1587,7 @@ def kv_append_paged_mla_bf16(c_new, k_pe_new, pool, block_table, seqlens, cu_q, 
     outside [cu_q[0], cu_q[B]) are neither read nor written. rope: "none" (the rotary dims are copied; no rope_table), "half" (pairs
     (i, i + 32)) or "interleaved" (pairs (2i, 2i + 1)), rotated in fp32 by rope_table fp32 [max_pos,64] (kv_append_rope_table(max_pos, 64)) with
     one rounding. Deterministic. C entry cln_kv_append_paged_mla_bf16 (include/cln_amd_ext.h); no CPU path."""
-    name = "kv_append_paged_mla_bf16"
-    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 9 + [ctypes.c_int] * 8 + [ctypes.c_void_p])
-    if rope not in _ROPE_MODES:
-        raise RuntimeError("%s: rope %r not supported ('none', 'half' or 'interleaved')" % (name, rope))
-    mode = _ROPE_MODES[rope]
-    if mode == 0 and rope_table is not None:
-        raise RuntimeError("%s: rope 'none' takes no rope_table" % name)
-    if mode != 0 and rope_table is None:
-        raise RuntimeError("%s: rope %r needs a rope_table (kv_append_rope_table(max_pos, 64))" % (name, rope))
-    if (q is None) != (q_out is None):
-        raise RuntimeError("%s: q and q_out are given together or not at all" % name)
-    _decode_check((c_new, k_pe_new, pool) + ((q, q_out) if q is not None else ()), (block_table, seqlens, cu_q), torch.bfloat16)
-    if c_new.dim() != 2 or k_pe_new.dim() != 2 or pool.dim() != 3 or block_table.dim() != 2:
-        raise RuntimeError("Tensor size mismatch!")
-    total_q = c_new.shape[0]
-    P, page, _ = pool.shape
-    B, max_pages = block_table.shape
-    _check_shape(c_new, total_q, _MLA_DC)
-    _check_shape(k_pe_new, total_q, _MLA_DR)
-    _check_shape(pool, P, page, _MLA_DK)
-    _check_shape(seqlens, B)
-    _check_shape(cu_q, B + 1)
-    Hq, max_pos = 1, 0
-    if q is not None:
-        if q.dim() != 3:
-            raise RuntimeError("Tensor size mismatch!")
-        Hq = q.shape[1]
-        _check_shape(q, total_q, Hq, _MLA_DK)
-        _check_shape(q_out, total_q, Hq, _MLA_DK)
-    if rope_table is not None:
-        _check_dtype(rope_table, torch.float32)
-        _check_dev(rope_table)
-        if rope_table.dim() != 2:
-            raise RuntimeError("Tensor size mismatch!")
-        max_pos = rope_table.shape[0]
-        _check_shape(rope_table, max_pos, _MLA_DR)
-    if page not in _PAGED_PAGES:
-        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    rc = fn(c_new.data_ptr(), k_pe_new.data_ptr(), pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), cu_q.data_ptr(), ptr(q), ptr(q_out),
-            ptr(rope_table), B, total_q, Hq, P, max_pages, page, max_pos, mode, _stream())
-    _raise(name, rc, "%s: max_pages * page or total_q too large for one launch" % name)
+    _mla_append("kv_append_paged_mla_bf16", c_new, k_pe_new, pool, block_table, seqlens, cu_q, None, q, q_out, rope_table, rope)
 
 
 # ---- the prompt path of multi-head latent attention (DESIGN 4.4.18): un-absorbed prefill (key 192 = 128 + 64 dims, value 128), the merge of
@@ -1523,9 +1607,7 @@ def fa2_prefill_varlen_mla_bf16(q, kv, k_pe, cu_q, cu_k, softmax_scale, out, lse
     cln_fa2_prefill_varlen_mla_bf16 (include/cln_amd_ext.h); no CPU path."""
     name = "fa2_prefill_varlen_mla_bf16"
     fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 7 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_void_p])
-    scale = float(softmax_scale)
-    if not (0.0 < scale < math.inf):
-        raise RuntimeError("%s: softmax_scale %r not supported (finite and > 0; there is no default)" % (name, softmax_scale))
+    scale = _softmax_scale(name, softmax_scale)
     _decode_check((q, kv, k_pe, out), (cu_q, cu_k), torch.bfloat16)
     if q.dim() != 3 or kv.dim() != 3 or k_pe.dim() != 2 or cu_q.dim() != 1:
         raise RuntimeError("Tensor size mismatch!")
@@ -1585,54 +1667,15 @@ def kv_gather_paged_mla_bf16(pool, block_table, cu_k, out, starts=None):
     torch.bfloat16 [total_k,576]. Packed row cu_k[b] + i receives cache row starts[b] + i of sequence b for i < cu_k[b+1] - cu_k[b], bit for
     bit; a cache row at or past max_pages * page is written as zeros and its table entry never followed; rows of no sequence are untouched. The
     mirror of kv_append_paged_mla_bf16. Deterministic. C entry cln_kv_gather_paged_mla_bf16 (include/cln_amd_ext.h); no CPU path."""
-    name = "kv_gather_paged_mla_bf16"
-    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_void_p])
-    _decode_check((pool, out), (block_table, cu_k) + (() if starts is None else (starts,)), torch.bfloat16)
-    if pool.dim() != 3 or block_table.dim() != 2 or out.dim() != 2:
-        raise RuntimeError("Tensor size mismatch!")
-    P, page, _ = pool.shape
-    B, max_pages = block_table.shape
-    total_k = out.shape[0]
-    _check_shape(pool, P, page, _MLA_DK)
-    _check_shape(out, total_k, _MLA_DK)
-    _check_shape(cu_k, B + 1)
-    if starts is not None:
-        _check_shape(starts, B)
-    if page not in _PAGED_PAGES:
-        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
-    rc = fn(pool.data_ptr(), block_table.data_ptr(), None if starts is None else starts.data_ptr(), cu_k.data_ptr(), out.data_ptr(), B, total_k,
-            P, max_pages, page, _stream())
-    _raise(name, rc, "%s: max_pages * page or total_k too large for one launch" % name)
+    _mla_gather("kv_gather_paged_mla_bf16", pool, block_table, cu_k, None, out, starts)
 
 
 # ---- multi-head latent attention over a paged latent cache held in FP8 (DESIGN 4.4.19): one pool torch.float8_e4m3fn [P,page,576] of rows
 # [c 512 | k_pe 64] in codes and one scale fp32 [1] on the GPU for the whole pool; everything else is bf16 as above
-def _mla_fp8_check(name, pool, kv_scale):
-    """What the MLA FP8 entries ask of the pool and its scale: a torch.float8_e4m3fn pool of three dims and an fp32 [1] scale on the GPU."""
-    _check_dtype(pool, torch.float8_e4m3fn)
-    _check_dtype(kv_scale, torch.float32)
-    _check_dev(pool, kv_scale)
-    _check_shape(kv_scale, 1)
-    if pool.dim() != 3:
-        raise RuntimeError("Tensor size mismatch!")
-
-
 def fa2_decode_paged_mla_bf16_fp8_plan(B, T, Hq, max_pages, page):
     """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_bf16_fp8: exactly fa2_decode_paged_mla_bf16_plan's, the key step is still 64 and
     D still 512 (cln_fa2_decode_paged_mla_bf16_fp8_plan, include/cln_amd_ext.h). T in 1 … 8, Hq in 1 … 128. No GPU needed."""
-    name = "fa2_decode_paged_mla_bf16_fp8"
-    B, T, Hq, max_pages, page = (int(x) for x in (B, T, Hq, max_pages, page))
-    rc, plan = _decode_plan("cln_%s_plan" % name, (B, T, Hq, max_pages, page))
-    if rc == -2:
-        if T > 8:
-            raise RuntimeError("%s: T %d not supported (1 … 8)" % (name, T))
-        if Hq > _MLA_MAX_HQ:
-            raise RuntimeError("%s: %d query heads not supported (1 … %d)" % (name, Hq, _MLA_MAX_HQ))
-        if page not in _PAGED_PAGES:
-            raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
-        raise RuntimeError("%s: max_pages * page or B * ceil(T * Hq / 64) * splits too large for one launch" % name)
-    _raise(name, rc)
-    return plan
+    return _mla_plan("fa2_decode_paged_mla_bf16_fp8", (B, T, Hq, max_pages, page), 8, _MLA_DECODE_TOO_LARGE)
 
 
 def fa2_decode_paged_mla_bf16_fp8(q, pool, block_table, seqlens, kv_scale, softmax_scale, out, lse=None, workspace=None):
@@ -1643,30 +1686,8 @@ def fa2_decode_paged_mla_bf16_fp8(q, pool, block_table, seqlens, kv_scale, softm
     exactly on the way to LDS; the fp32 score multiplier is (softmax_scale * log2(e)) * kv_scale and kv_scale multiplies the fp32 result in front
     of its store. workspace: at least fa2_decode_paged_mla_bf16_fp8_plan(...)[2] bytes; allocated here when None and the plan splits the keys.
     Deterministic. C entry cln_fa2_decode_paged_mla_bf16_fp8 (include/cln_amd_ext.h); no CPU path."""
-    name = "fa2_decode_paged_mla_bf16_fp8"
-    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 8 + [ctypes.c_longlong] + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_void_p])
-    scale = float(softmax_scale)
-    if not (0.0 < scale < math.inf):
-        raise RuntimeError("%s: softmax_scale %r not supported (finite and > 0; there is no default)" % (name, softmax_scale))
-    _decode_check((q, out), (block_table, seqlens), torch.bfloat16)
-    _mla_fp8_check(name, pool, kv_scale)
-    if q.dim() != 4 or block_table.dim() != 2:
-        raise RuntimeError("Tensor size mismatch!")
-    B, T, Hq, Dk = q.shape
-    P, page, _ = pool.shape
-    if Dk != _MLA_DK:
-        raise RuntimeError("%s: q of %d dims not supported (%d = 512 latent + 64 rotary)" % (name, Dk, _MLA_DK))
-    _check_shape(pool, P, page, _MLA_DK)
-    if block_table.shape[0] != B:
-        raise RuntimeError("Tensor size mismatch!")
-    max_pages = block_table.shape[1]
-    _check_shape(out, B, T, Hq, _MLA_DC)
-    _check_shape(seqlens, B)
-    lse_ptr = _decode_lse(lse, B, T, Hq)
-    ws_ptr, ws_bytes = _decode_workspace(name, fa2_decode_paged_mla_bf16_fp8_plan(B, T, Hq, max_pages, page)[2], workspace, q.device)
-    rc = fn(q.data_ptr(), pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), kv_scale.data_ptr(), out.data_ptr(), lse_ptr, ws_ptr,
-            ws_bytes, B, T, Hq, P, max_pages, page, scale, _stream())
-    _raise(name, rc)
+    _mla_decode("fa2_decode_paged_mla_bf16_fp8", fa2_decode_paged_mla_bf16_fp8_plan, q, pool, block_table, seqlens, kv_scale, None, softmax_scale,
+                out, lse, workspace)
 
 
 def kv_append_paged_mla_bf16_fp8(c_new, k_pe_new, pool, block_table, seqlens, cu_q, kv_scale, q=None, q_out=None, rope_table=None, rope="none"):
@@ -1676,49 +1697,7 @@ def kv_append_paged_mla_bf16_fp8(c_new, k_pe_new, pool, block_table, seqlens, cu
     in between. q, q_out torch.bfloat16 [total_q,Hq,576] (q_out may be q), cu_q, block_table, seqlens, rope_table, the three rope modes, liveness
     and the untouched rows of no sequence as there. Deterministic. C entry cln_kv_append_paged_mla_bf16_fp8 (include/cln_amd_ext.h); no CPU
     path."""
-    name = "kv_append_paged_mla_bf16_fp8"
-    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 10 + [ctypes.c_int] * 8 + [ctypes.c_void_p])
-    if rope not in _ROPE_MODES:
-        raise RuntimeError("%s: rope %r not supported ('none', 'half' or 'interleaved')" % (name, rope))
-    mode = _ROPE_MODES[rope]
-    if mode == 0 and rope_table is not None:
-        raise RuntimeError("%s: rope 'none' takes no rope_table" % name)
-    if mode != 0 and rope_table is None:
-        raise RuntimeError("%s: rope %r needs a rope_table (kv_append_rope_table(max_pos, 64))" % (name, rope))
-    if (q is None) != (q_out is None):
-        raise RuntimeError("%s: q and q_out are given together or not at all" % name)
-    _decode_check((c_new, k_pe_new) + ((q, q_out) if q is not None else ()), (block_table, seqlens, cu_q), torch.bfloat16)
-    _mla_fp8_check(name, pool, kv_scale)
-    if c_new.dim() != 2 or k_pe_new.dim() != 2 or block_table.dim() != 2:
-        raise RuntimeError("Tensor size mismatch!")
-    total_q = c_new.shape[0]
-    P, page, _ = pool.shape
-    B, max_pages = block_table.shape
-    _check_shape(c_new, total_q, _MLA_DC)
-    _check_shape(k_pe_new, total_q, _MLA_DR)
-    _check_shape(pool, P, page, _MLA_DK)
-    _check_shape(seqlens, B)
-    _check_shape(cu_q, B + 1)
-    Hq, max_pos = 1, 0
-    if q is not None:
-        if q.dim() != 3:
-            raise RuntimeError("Tensor size mismatch!")
-        Hq = q.shape[1]
-        _check_shape(q, total_q, Hq, _MLA_DK)
-        _check_shape(q_out, total_q, Hq, _MLA_DK)
-    if rope_table is not None:
-        _check_dtype(rope_table, torch.float32)
-        _check_dev(rope_table)
-        if rope_table.dim() != 2:
-            raise RuntimeError("Tensor size mismatch!")
-        max_pos = rope_table.shape[0]
-        _check_shape(rope_table, max_pos, _MLA_DR)
-    if page not in _PAGED_PAGES:
-        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    rc = fn(c_new.data_ptr(), k_pe_new.data_ptr(), pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), cu_q.data_ptr(),
-            kv_scale.data_ptr(), ptr(q), ptr(q_out), ptr(rope_table), B, total_q, Hq, P, max_pages, page, max_pos, mode, _stream())
-    _raise(name, rc, "%s: max_pages * page or total_q too large for one launch" % name)
+    _mla_append("kv_append_paged_mla_bf16_fp8", c_new, k_pe_new, pool, block_table, seqlens, cu_q, kv_scale, q, q_out, rope_table, rope)
 
 
 def kv_gather_paged_mla_bf16_fp8(pool, block_table, cu_k, kv_scale, out, starts=None):
@@ -1726,25 +1705,7 @@ def kv_gather_paged_mla_bf16_fp8(pool, block_table, cu_k, kv_scale, out, starts=
     torch.bfloat16 [total_k,576]; each element is bf16(fp32(code) * kv_scale), one rounding. block_table, cu_k, starts, the zeros for a cache row
     at or past max_pages * page and the untouched rows of no sequence as there: the context-chunk loop of the prompt path runs unchanged over an
     FP8 pool. Deterministic. C entry cln_kv_gather_paged_mla_bf16_fp8 (include/cln_amd_ext.h); no CPU path."""
-    name = "kv_gather_paged_mla_bf16_fp8"
-    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 5 + [ctypes.c_void_p])
-    _decode_check((out,), (block_table, cu_k) + (() if starts is None else (starts,)), torch.bfloat16)
-    _mla_fp8_check(name, pool, kv_scale)
-    if block_table.dim() != 2 or out.dim() != 2:
-        raise RuntimeError("Tensor size mismatch!")
-    P, page, _ = pool.shape
-    B, max_pages = block_table.shape
-    total_k = out.shape[0]
-    _check_shape(pool, P, page, _MLA_DK)
-    _check_shape(out, total_k, _MLA_DK)
-    _check_shape(cu_k, B + 1)
-    if starts is not None:
-        _check_shape(starts, B)
-    if page not in _PAGED_PAGES:
-        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
-    rc = fn(pool.data_ptr(), block_table.data_ptr(), None if starts is None else starts.data_ptr(), cu_k.data_ptr(), kv_scale.data_ptr(),
-            out.data_ptr(), B, total_k, P, max_pages, page, _stream())
-    _raise(name, rc, "%s: max_pages * page or total_k too large for one launch" % name)
+    _mla_gather("kv_gather_paged_mla_bf16_fp8", pool, block_table, cu_k, kv_scale, out, starts)
 
 
 # ---- sparse multi-head latent attention over the paged latent cache (DESIGN 4.4.20): DeepSeek-V3.2's attention behind its indexer. The pool,
@@ -1753,17 +1714,8 @@ def fa2_decode_paged_mla_sparse_bf16_plan(B, T, Hq, topk, max_pages, page):
     """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_sparse_bf16: a function of the shape only; the splits divide the topk index slots
     of a query token, not the context (cln_fa2_decode_paged_mla_sparse_bf16_plan, include/cln_amd_ext.h). T >= 1 (no cap: a query token is its
     own workgroup job), Hq in 1 … 128, topk >= 1. No GPU needed."""
-    name = "fa2_decode_paged_mla_sparse_bf16"
-    B, T, Hq, topk, max_pages, page = (int(x) for x in (B, T, Hq, topk, max_pages, page))
-    rc, plan = _decode_plan("cln_%s_plan" % name, (B, T, Hq, topk, max_pages, page))
-    if rc == -2:
-        if Hq > _MLA_MAX_HQ:
-            raise RuntimeError("%s: %d query heads not supported (1 … %d)" % (name, Hq, _MLA_MAX_HQ))
-        if page not in _PAGED_PAGES:
-            raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
-        raise RuntimeError("%s: max_pages * page, B * T * Hq or B * T * ceil(Hq / 64) * splits too large for one launch" % name)
-    _raise(name, rc)
-    return plan
+    return _mla_plan("fa2_decode_paged_mla_sparse_bf16", (B, T, Hq, topk, max_pages, page), None,
+                     "%s: max_pages * page, B * T * Hq or B * T * ceil(Hq / 64) * splits too large for one launch")
 
 
 def fa2_decode_paged_mla_sparse_bf16(q, pool, block_table, seqlens, indices, softmax_scale, out, lse=None, workspace=None):
@@ -1777,33 +1729,8 @@ def fa2_decode_paged_mla_sparse_bf16(q, pool, block_table, seqlens, indices, sof
     twice is two keys: pass distinct positions. softmax_scale required, finite and > 0; Hq in 1 … 128; any T >= 1 (also V3.2's sparse prefill
     over the paged cache); any topk >= 1. workspace: at least fa2_decode_paged_mla_sparse_bf16_plan(...)[2] bytes; allocated here when None and
     the plan splits the list. Deterministic. C entry cln_fa2_decode_paged_mla_sparse_bf16 (include/cln_amd_ext.h); no CPU path."""
-    name = "fa2_decode_paged_mla_sparse_bf16"
-    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 8 + [ctypes.c_longlong] + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_void_p])
-    scale = float(softmax_scale)
-    if not (0.0 < scale < math.inf):
-        raise RuntimeError("%s: softmax_scale %r not supported (finite and > 0; there is no default)" % (name, softmax_scale))
-    _decode_check((q, pool, out), (block_table, seqlens, indices), torch.bfloat16)
-    if q.dim() != 4 or pool.dim() != 3 or block_table.dim() != 2 or indices.dim() != 3:
-        raise RuntimeError("Tensor size mismatch!")
-    B, T, Hq, Dk = q.shape
-    P, page, _ = pool.shape
-    topk = indices.shape[2]
-    if Dk != _MLA_DK:
-        raise RuntimeError("%s: q of %d dims not supported (%d = 512 latent + 64 rotary)" % (name, Dk, _MLA_DK))
-    _check_shape(pool, P, page, _MLA_DK)
-    if block_table.shape[0] != B:
-        raise RuntimeError("Tensor size mismatch!")
-    max_pages = block_table.shape[1]
-    _check_shape(out, B, T, Hq, _MLA_DC)
-    _check_shape(seqlens, B)
-    _check_shape(indices, B, T, topk)
-    if not indices.is_contiguous():
-        raise RuntimeError("%s: indices must be contiguous [B,T,topk]" % name)
-    lse_ptr = _decode_lse(lse, B, T, Hq)
-    ws_ptr, ws_bytes = _decode_workspace(name, fa2_decode_paged_mla_sparse_bf16_plan(B, T, Hq, topk, max_pages, page)[2], workspace, q.device)
-    rc = fn(q.data_ptr(), pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), indices.data_ptr(), out.data_ptr(), lse_ptr, ws_ptr,
-            ws_bytes, B, T, Hq, topk, P, max_pages, page, scale, _stream())
-    _raise(name, rc)
+    _mla_decode("fa2_decode_paged_mla_sparse_bf16", fa2_decode_paged_mla_sparse_bf16_plan, q, pool, block_table, seqlens, None, indices,
+                softmax_scale, out, lse, workspace)
 
 
 # ---- the indexer of DeepSeek-V3.2's sparse attention (DESIGN 4.4.22): a paged cache of index keys (128 dims a token) next to the latent cache,
@@ -1832,7 +1759,7 @@ def kv_append_paged_index_bf16(k_idx_new, idx_pool, block_table, seqlens, cu_q):
     _check_shape(seqlens, B)
     _check_shape(cu_q, B + 1)
     if page not in _PAGED_PAGES:
-        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+        raise _paged_page_error(name, page)
     rc = fn(k_idx_new.data_ptr(), idx_pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), cu_q.data_ptr(), B, total_q, P, max_pages,
             page, _stream())
     _raise(name, rc, "%s: max_pages * page too large for one launch" % name)
@@ -1870,7 +1797,7 @@ def mla_index_logits_paged_bf16(q_idx, weights, idx_pool, block_table, seqlens, 
     if Hi > _IDX_MAX_HEADS:
         raise RuntimeError("%s: %d index heads not supported (1 … %d)" % (name, Hi, _IDX_MAX_HEADS))
     if page not in _PAGED_PAGES:
-        raise RuntimeError("%s: page size %d not supported (16, 32, 64, 128 or 256)" % (name, page))
+        raise _paged_page_error(name, page)
     rc = fn(q_idx.data_ptr(), weights.data_ptr(), idx_pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), logits.data_ptr(), B, T, Hi,
             ld, P, max_pages, page, _stream())
     _raise(name, rc, "%s: max_pages * page, B * T or B * T * ceil(cap / 1024) too large for one launch" % name)
