@@ -564,6 +564,24 @@ def mla_index_topk(logits, seqlens, topk, indices):
     return host.mla_index_topk(logits, seqlens, topk, indices)
 
 
+def fa2_decode_paged_mla_sparse_bf16_fp8(q, pool, block_table, seqlens, kv_scale, indices, softmax_scale, out, lse=None, workspace=None):
+    """fa2_decode_paged_mla_sparse_bf16 over a latent cache held in FP8 (a DeepSeek-V3.2 step on the pool kv_append_paged_mla_bf16_fp8 writes):
+    pool torch.float8_e4m3fn [P,page,576] of rows [c 512 | k_pe 64] in codes, kv_scale fp32 [1] on the GPU (one scale for the whole pool: value
+    = e4m3(code) * kv_scale); q bf16 [B,T,Hq,576] absorbed, indices int32 [B,T,topk] on the GPU with the validity rule, the empty slots and the
+    duplicates of the bf16 entry, out bf16 [B,T,Hq,512], lse fp32 [B,T,Hq] or None, softmax_scale required, any T >= 1. The workspace is sized
+    by fa2_decode_paged_mla_sparse_bf16_fp8_plan. C entry cln_fa2_decode_paged_mla_sparse_bf16_fp8 (include/cln_amd_ext.h). Not a reference
+    name."""
+    from . import host
+    return host.fa2_decode_paged_mla_sparse_bf16_fp8(q, pool, block_table, seqlens, kv_scale, indices, softmax_scale, out, lse, workspace)
+
+
+def fa2_decode_paged_mla_sparse_bf16_fp8_plan(B, T, Hq, topk, max_pages, page):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_sparse_bf16_fp8: exactly fa2_decode_paged_mla_sparse_bf16_plan's. C entry
+    cln_fa2_decode_paged_mla_sparse_bf16_fp8_plan."""
+    from . import host
+    return host.fa2_decode_paged_mla_sparse_bf16_fp8_plan(B, T, Hq, topk, max_pages, page)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

@@ -24,6 +24,7 @@
 // __launch_bounds__(256, 1) and the unified file of 512. LDS: the sibling's one image, 64 x 1184 = 75776 bytes static.
 #pragma once
 #include "flash_attn_paged_bf16_fp8_rows.cuh"  // e4m3x8_to_b8; paged_bf16.cuh
+#include "flash_attn_decode_paged_mla_shared.cuh"  // store_split_scaled
 
 namespace fa2b {
 
@@ -45,18 +46,6 @@ struct PagedLatent8 {
   int max_pages, page_shift;
   __host__ __device__ int nmax() const { return max_pages << page_shift; }  // the plan checked that it fits
 };
-
-// store_split with kv_scale in front of the store: S = 1 the finished row (O / L) kv_scale rounded once, else the partial O kv_scale
-template <int D>
-__device__ __forceinline__ void store_split_scaled(const Out& out, size_t row, int t, unsigned s, int S, float mx, float L, float O, float kvs) {
-  if (S == 1) {
-    const float inv = L > 0.0f ? 1.0f / L : 0.0f;
-    out.o[row * D + t] = (bf16_t)(O * inv * kvs);
-    if (out.lse && t == 0) out.lse[row] = L > 0.0f ? (mx + __builtin_log2f(L)) * 0.6931471805599453f : FA2D_NEG_INF;
-  } else {
-    store_split<D>(out, row, t, s, S, mx, L, O * kvs);
-  }
-}
 
 __global__ __launch_bounds__(kThreads, 1) void fa2_decode_paged_mla_bf16_fp8_mfma(const bf16_t* __restrict__ q, const PagedLatent8 kv,
                                                                                   const int* __restrict__ seqlens,

@@ -22,14 +22,14 @@
 // LDS.) A step none of whose 64 slots is valid skips both products: with every score -inf they would change no bit.
 //
 // All S splits of a row are always written -- an empty one as m = -inf, l = 0, O = 0 -- and no workgroup returns early on the lengths: which
-// splits are live is not a function of seqlens here. fa2_decode_combine_bf16_all<512> below merges all S partials in ascending order with the
+// splits are live is not a function of seqlens here. fa2_decode_combine_bf16_all<512> (flash_attn_decode_paged_mla_shared.cuh) merges all S partials in ascending order with the
 // family's -inf guard.
 //
 // Registers per wave (the budget, written before the kernel; DESIGN 4.4.20 has the compiled numbers): the sibling's about 320 (128
 // accumulators + 72 Q + 72 of the next step's rows + scores, P, fragments, addresses) + two indices, a page and a flag in flight + four flag
 // words: __launch_bounds__(256, 1) and the unified file of 512. LDS: the sibling's one image, 64 x 1184 = 75776 bytes static.
 #pragma once
-#include "paged_bf16.cuh"
+#include "flash_attn_decode_paged_mla_shared.cuh"  // fa2_decode_combine_bf16_all; paged_bf16.cuh
 
 namespace fa2b {
 
@@ -203,27 +203,6 @@ __global__ __launch_bounds__(kThreads, 1) void fa2_decode_paged_mla_sparse_bf16_
 #pragma unroll
       for (int e = 0; e < 4; ++e) store_split<DV>(out, row, 16 * db + 4 * g4 + e, s, S, m, l, acc[db][e]);
   }
-}
-
-// fa2_decode_combine_bf16_rows without the liveness rule: every one of the S partials of a row was written (an empty split as (-inf, 0, 0)),
-// all are merged in ascending s with the same -inf guard. One workgroup of D threads per output row.
-template <int D>
-__global__ __launch_bounds__(D) void fa2_decode_combine_bf16_all(const float* __restrict__ ws_o, const float* __restrict__ ws_ml,
-                                                                 bf16_t* __restrict__ o, float* __restrict__ lse, int S) {
-  const unsigned row = blockIdx.x;
-  const int t = threadIdx.x;
-  const float* ml = ws_ml + (size_t)row * S * 2;
-  const float* po = ws_o + (size_t)row * S * D + t;
-  float mx = FA2D_NEG_INF;
-  for (int s = 0; s < S; ++s) mx = fmaxf(mx, ml[2 * s]);
-  const float ms = mx == FA2D_NEG_INF ? 0.0f : mx;  // never exp2(-inf + inf)
-  float L = 0.0f, O = 0.0f;
-  for (int s = 0; s < S; ++s) {
-    const float f = fa2d::ex2(ml[2 * s] - ms);
-    L = fmaf(ml[2 * s + 1], f, L);
-    O = fmaf(po[(size_t)s * D], f, O);
-  }
-  store_final<D>(Out{o, lse, nullptr, nullptr}, row, t, mx, L, O);
 }
 
 // S splits of C index slots (C a multiple of the 64-slot step, S C >= topk > (S - 1) C: paged::mla_sparse_plan). No host read of the table,

@@ -1733,6 +1733,33 @@ def fa2_decode_paged_mla_sparse_bf16(q, pool, block_table, seqlens, indices, sof
                 softmax_scale, out, lse, workspace)
 
 
+# ---- the same over the latent cache held in FP8: the pool and its scale are fa2_decode_paged_mla_bf16_fp8's, the lists and every
+# rule about them the entry's above
+_MLA_SPARSE_TOO_LARGE = "%s: max_pages * page, B * T * Hq or B * T * ceil(Hq / 64) * splits too large for one launch"
+
+
+def fa2_decode_paged_mla_sparse_bf16_fp8_plan(B, T, Hq, topk, max_pages, page):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_sparse_bf16_fp8: exactly fa2_decode_paged_mla_sparse_bf16_plan's, the slot step is
+    still 64 and D still 512 (cln_fa2_decode_paged_mla_sparse_bf16_fp8_plan, include/cln_amd_ext.h). T >= 1, Hq in 1 … 128, topk >= 1. No GPU
+    needed."""
+    return _mla_plan("fa2_decode_paged_mla_sparse_bf16_fp8", (B, T, Hq, topk, max_pages, page), None, _MLA_SPARSE_TOO_LARGE)
+
+
+def fa2_decode_paged_mla_sparse_bf16_fp8(q, pool, block_table, seqlens, kv_scale, indices, softmax_scale, out, lse=None, workspace=None):
+    """fa2_decode_paged_mla_sparse_bf16 over a latent cache held in FP8: the attention of a DeepSeek-V3.2 step on the pool
+    kv_append_paged_mla_bf16_fp8 writes. q torch.bfloat16 [B,T,Hq,576], absorbed; pool torch.float8_e4m3fn [P,page,576] of rows
+    [c 512 | k_pe 64] in codes; kv_scale fp32 [1] on the GPU, one scale for the whole pool: a stored byte c means e4m3(c) * kv_scale (finite and
+    > 0, no NaN byte in a listed row: the caller's contract, not checked; an unlisted row is never read); indices int32 [B,T,topk], contiguous,
+    on the GPU, with the validity rule 0 <= idx < vis(b,t), the empty slots anywhere, the duplicates (two keys) and the O = 0, LSE = -inf of a
+    token without a valid slot exactly as there; block_table, seqlens, out torch.bfloat16 [B,T,Hq,512], lse, softmax_scale (required, finite
+    and > 0), any T >= 1, Hq in 1 … 128, any topk >= 1 and the pages as there. The codes are converted to bf16 exactly on the way to LDS; the
+    fp32 score multiplier is (softmax_scale * log2(e)) * kv_scale and kv_scale multiplies the fp32 result in front of its store. workspace: at
+    least fa2_decode_paged_mla_sparse_bf16_fp8_plan(...)[2] bytes; allocated here when None and the plan splits the list. Deterministic. C entry
+    cln_fa2_decode_paged_mla_sparse_bf16_fp8 (include/cln_amd_ext.h); no CPU path."""
+    _mla_decode("fa2_decode_paged_mla_sparse_bf16_fp8", fa2_decode_paged_mla_sparse_bf16_fp8_plan, q, pool, block_table, seqlens, kv_scale,
+                indices, softmax_scale, out, lse, workspace)
+
+
 # ---- the indexer of DeepSeek-V3.2's sparse attention (DESIGN 4.4.22): a paged cache of index keys (128 dims a token) next to the latent cache,
 # behind the same block table; the logits of every visible cache position for a query token; the exact top-k of a row of logits, the list
 # fa2_decode_paged_mla_sparse_bf16 takes

@@ -685,6 +685,27 @@ int cln_mla_index_logits_paged_bf16_describe(int B, int T, int Hi, long long ld,
 int cln_mla_index_topk(const float* logits, const int* seqlens, int* indices, int B, int T, long long ld, int topk, void* stream);
 int cln_mla_index_topk_describe(int B, int T, long long ld, int topk, char* buf, int len);
 
+/* ---- Sparse MLA decode over the paged latent cache held in FP8 (OCP e4m3fn), bf16 queries: the attention of a
+ * DeepSeek-V3.2 step on the pool cln_kv_append_paged_mla_bf16_fp8 writes. Semantics are exactly cln_fa2_decode_paged_mla_sparse_bf16's -- a
+ * slot valid iff 0 <= idx < vis(b,t), empty slots anywhere that address no table entry and no pool row, a position listed twice two keys, no
+ * valid slot O = 0 and LSE = -inf, T without a cap, Hq in 1 ... 128, any topk >= 1 -- on cln_fa2_decode_paged_mla_bf16_fp8's pool: codes
+ * [P,page,576] of bytes and kv_scale fp32 [1] ON THE DEVICE, value = e4m3(code) kv_scale; the caller guarantees a finite kv_scale > 0 and no
+ * NaN code in a LISTED row (an unlisted row is never read). The codes are converted to bf16 exactly on the way to LDS, once per workgroup; the
+ * fp32 score multiplier is (softmax_scale log2 e) kv_scale and kv_scale multiplies the fp32 result in front of its store, so the partials of a
+ * split carry it. With kv_scale a power of two O and LSE equal cln_fa2_decode_paged_mla_sparse_bf16's on the pool dequantised to bf16 bit for
+ * bit; on the dense list [0 ... vis - 1, -1 ...] they equal cln_fa2_decode_paged_mla_bf16_fp8's.
+ * Status, in the siblings' order: the scale (-1); a missing or misaligned pointer (q, pool, o, lse, workspace 16 bytes; block_table, seqlens,
+ * kv_scale, indices 4 bytes) or an output equal to an input or another output (-1); P <= 0 (-1); the plan (-1 / -2 as there); a workspace
+ * smaller than the plan's (-1). _plan returns what cln_fa2_decode_paged_mla_sparse_bf16_plan returns, status included. Deterministic.
+ */
+int cln_fa2_decode_paged_mla_sparse_bf16_fp8_plan(int B, int T, int Hq, int topk, int max_pages, int page, int* splits, int* chunk,
+                                                  long long* workspace_bytes);
+int cln_fa2_decode_paged_mla_sparse_bf16_fp8(const void* q, const void* pool, const int* block_table, const int* seqlens, const float* kv_scale,
+                                             const int* indices, void* o, float* lse, void* workspace, long long workspace_bytes, int B, int T,
+                                             int Hq, int topk, int P, int max_pages, int page, float softmax_scale, void* stream);
+int cln_fa2_decode_paged_mla_sparse_bf16_fp8_describe(int B, int T, int Hq, int topk, int max_pages, int page, float softmax_scale, char* buf,
+                                                      int len);
+
 #ifdef __cplusplus
 }
 #endif
