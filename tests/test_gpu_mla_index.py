@@ -6,7 +6,11 @@ behind the table entries past a sequence's pages, NaN behind q_idx and weights).
 tolerance. Then independence, replay, 4-byte aligned operands, a captured graph of a whole V3.2 attention step, and the chain into
 fa2_decode_paged_mla_sparse_bf16. Every parity case prints err / bound before it asserts (pytest -s); the last test prints the largest.
 
-Largest err / bound seen on an MI355X: see DESIGN 4.4.22 and profiles/r32_mla_index_tests.log."""
+Also here: every head-block count of the logits kernel (Hi 32 ... 63), pages 32, 128 and 256, a negative length, and the edges of the
+append's contract. The long rows of the top-k, the rows at every 4-byte residue and the pools and tensors past 2^32 elements are in
+tests/test_gpu_mla_index_long_rows.py, _large_pool.py and _large_rows.py, which use this file's helpers.
+
+Largest err / bound seen on an MI355X: see DESIGN 4.4.22 and profiles/r32_mla_index_tests.log, profiles/r34_mla_index_tests.log."""
 import os
 import sys
 
@@ -86,7 +90,9 @@ def check_logits(got, ref, bound, vis, label):
     return worst
 
 
-def run_topk(logits, lens, topk, shift=False):
+def run_topk(logits, lens, topk, shift=False, ptrs=None):
+    """indices [B,T,topk] on the CPU, pre-filled with ISENT inside guard bands that must keep it. ptrs: a list that receives data_ptr() of
+    the logits on the device."""
     B, T, ld = logits.shape
     dv = "cuda"
     place = off4 if shift else (lambda t: t.to(dv))
@@ -94,7 +100,10 @@ def run_topk(logits, lens, topk, shift=False):
     big = torch.full(((B + 2) * T * topk + 8,), ISENT, dtype=torch.int32, device=dv)
     idx = big[T * topk + o:T * topk + o + B * T * topk].view(B, T, topk)
     assert not shift or idx.data_ptr() % 16 == 4
-    pkg().mla_index_topk(place(logits), place(torch.tensor(lens, dtype=torch.int32)), topk, idx)
+    ld_ = place(logits)
+    if ptrs is not None:
+        ptrs.append(ld_.data_ptr())
+    pkg().mla_index_topk(ld_, place(torch.tensor(lens, dtype=torch.int32)), topk, idx)
     torch.cuda.synchronize()
     flat = big.cpu()
     assert bool((flat[:T * topk + o] == ISENT).all()) and bool((flat[T * topk + o + B * T * topk:] == ISENT).all()), "guard bands of indices"
@@ -102,6 +111,54 @@ def run_topk(logits, lens, topk, shift=False):
 
 
 # ---------------------------------------------------------------------------------------------------- 1. logits against the bound
+
+def test_describe_names_the_three_head_block_kernel(built):
+    """Hi = 33 ... 48 launch mla_index_logits_paged_bf16_mfma<3>; the shapes below are tested further down."""
+    m = pkg().manifest
+    for Hi, T, nhb in ((32, 3, 2), (33, 3, 3), (48, 1, 3), (49, 1, 4), (63, 3, 4)):
+        text = m.describe_mla_index_logits_paged_bf16(len(ix.ONE_LENS), T, Hi, ix.ONE_NMAX, ix.ONE_NMAX // 16, 16)
+        assert text.startswith("mla_index_logits_paged_bf16_mfma<NHB=%d> T=%d Hi=%d " % (nhb, T, Hi)), text[:80]
+
+
+@pytest.mark.parametrize("HT", ix.ONE_HT_MORE, ids=lambda ht: "Hi%dxT%d" % ht)
+def test_logits_within_the_bound_at_every_head_block_count(built, dev, HT):
+    """Hi 32, 33, 48, 49, 63 at page 16: NHB = 2 (a full second block, no padding heads), 3, 3 (the instantiation no other test launches,
+    at both of its ends), 4, 4; the bound is test_logits_within_the_bound's."""
+    Hi, T = HT
+    q, w, (pool, bt), lens, ld = ix.one_case(Hi, T, 16)
+    ref, bound, vis = ix.reference("one", Hi, T, 16)
+    check_logits(run_logits(q, w, pool, bt, lens, ld), ref, bound, vis, "logits head blocks: Hi=%d T=%d NHB=%d" % (Hi, T, -(-Hi // 16)))
+
+
+@pytest.mark.parametrize("page", [32, 128, 256])
+def test_logits_within_the_bound_at_the_other_pages(built, dev, page):
+    """(Hi, T) = (17, 8) behind pages of 32, 128 and 256 rows (Nmax 320, 512, 4096): at page 256 the sixteen table entries a wave loads at
+    once are one entry, and the sequence of 257 keys has one row in its second page."""
+    Hi, T = ix.PAGED_HT
+    q, w, (pool, bt), lens, ld = ix.paged_case(page)
+    assert pool.shape[1] == page and bt.shape[1] * page == ld
+    ref, bound, vis = ix.logits_ref(q, w, pool, bt, lens, ld)
+    check_logits(run_logits(q, w, pool, bt, lens, ld), ref, bound, vis, "logits pages: Hi=%d T=%d page=%d" % (Hi, T, page))
+
+
+@pytest.mark.parametrize("page", [32, 128, 256])
+def test_logits_several_chunks_at_the_other_pages(built, dev, page):
+    """long_case's problem (Nmax 4096, four chunks) behind pages of 32, 128 and 256 rows."""
+    q, w, (pool, bt), lens, ld = ix.long_case_paged(page)
+    ref, bound, vis = ix.logits_ref(q, w, pool, bt, lens, ld)
+    check_logits(run_logits(q, w, pool, bt, lens, ld), ref, bound, vis, "logits several chunks, pages: page=%d" % page)
+
+
+def test_logits_with_a_negative_length_writes_nothing_for_it(built, dev):
+    """max(seqlens[b], 0): the sequence of length -5 keeps the sentinel in all of its rows; its neighbours are within the bound."""
+    q, w, (pool, bt), lens, ld = ix.neg_case()
+    assert lens[1] == -5
+    ref, bound, vis = ix.logits_ref(q, w, pool, bt, lens, ld)
+    assert all(v <= 0 for v in vis[1])
+    got = run_logits(q, w, pool, bt, lens, ld)
+    check_logits(got, ref, bound, vis, "logits negative length: Hi=17 T=3")
+    assert bool((ibits(got[1]) == SENT).all())
+
 
 @pytest.mark.parametrize("page", [16, 64])
 @pytest.mark.parametrize("HT", ix.ONE_HT, ids=lambda ht: "Hi%dxT%d" % ht)
@@ -134,17 +191,27 @@ def test_logits_cap_is_the_smaller_of_the_cache_and_ld(built, dev, ld):
 
 # ---------------------------------------------------------------------------------------------------- 2. exact answers
 
-def test_logits_exact_integers(built, dev):
-    """Integer q, k in [-4, 4] and weights +- 2^e: bit equality with the fp64 reference (tests/test_mla_index_surface.py proves that every
-    partial sum stays below 2^24 quarter units)."""
-    q, w, (pool, bt), lens, ld = ix.exact_case()
+def _exact(Hi, tail_nan=False):
+    q, w, (pool, bt), lens, ld = ix.exact_case(Hi, 3, 16)
     ref, _, vis = ix.logits_ref(q, w, pool, bt, lens, ld)
-    got = run_logits(q, w, pool, bt, lens, ld)
+    got = run_logits(q, w, pool, bt, lens, ld, tail_nan=tail_nan)
     for b in range(len(lens)):
         for t in range(q.shape[1]):
             n = max(vis[b][t], 0)
-            assert torch.equal(got[b, t, :n].double(), ref[b, t, :n]), (b, t)
+            assert torch.equal(got[b, t, :n].double(), ref[b, t, :n]), (Hi, b, t)
             assert bool((ibits(got[b, t, n:]) == SENT).all())
+
+
+def test_logits_exact_integers(built, dev):
+    """Integer q, k in [-4, 4] and weights +- 2^e: bit equality with the fp64 reference (tests/test_mla_index_surface.py proves that every
+    partial sum stays below 2^24 quarter units)."""
+    _exact(64)
+
+
+@pytest.mark.parametrize("Hi", [48, 33])
+def test_logits_exact_integers_on_three_head_blocks(built, dev, Hi):
+    """The same at Hi = 48 and 33: both ends of mla_index_logits_paged_bf16_mfma<3>, the second with 15 padding heads."""
+    _exact(Hi)
 
 
 def test_logits_all_negative_products_are_plus_zero(built, dev):
@@ -164,13 +231,15 @@ def test_logits_all_negative_products_are_plus_zero(built, dev):
 
 def test_logits_padding_heads_contribute_nothing(built, dev):
     """Hi = 17: the heads 17 ... 31 of the second block of 16 would read the bytes behind q_idx and weights, which hold NaN here."""
-    q, w, (pool, bt), lens, ld = ix.exact_case(17, 3, 16)
-    ref, _, vis = ix.logits_ref(q, w, pool, bt, lens, ld)
-    got = run_logits(q, w, pool, bt, lens, ld, tail_nan=True)
-    for b in range(len(lens)):
-        for t in range(3):
-            n = max(vis[b][t], 0)
-            assert torch.equal(got[b, t, :n].double(), ref[b, t, :n]), (b, t)
+    _exact(17, tail_nan=True)
+
+
+@pytest.mark.parametrize("Hi", [33, 49])
+def test_logits_padding_heads_of_the_third_and_fourth_block(built, dev, Hi):
+    """Hi = 33, 49: fifteen padding heads in the last of three and of four blocks, NaN behind q_idx and weights. The surface test's proof
+    that every partial sum stays below 2^24 quarter units was written for Hi = 64; these cases sum over fewer heads, so it covers them (the
+    surface test runs it at these Hi too)."""
+    _exact(Hi, tail_nan=True)
 
 
 # ---------------------------------------------------------------------------------------------------- 3. top-k, exact
@@ -236,6 +305,40 @@ def test_append_writes_its_rows_and_nothing_else(built, dev):
                                      torch.tensor(cu, dtype=torch.int32, device=dv))
     torch.cuda.synchronize()
     assert torch.equal(pd.cpu().view(torch.int16), want.view(torch.int16))
+
+
+def _run_append(p, shift=False):
+    """The pool after the append on the device, inside a guard page on each side; every byte starts as ix.MARK. Returns (pool on the CPU,
+    the two guard pages)."""
+    dv = "cuda"
+    place = off4 if shift else (lambda t: t.to(dv))
+    page, P = p["page"], p["P"]
+    whole = torch.full((P + 2, page, ix.D), ix.MARK, dtype=torch.int16, device=dv).view(BF)
+    pd = whole[1:P + 1]
+    assert pd.is_contiguous() and pd.data_ptr() % 16 == 0
+    pkg().kv_append_paged_index_bf16(p["k_new"].to(dv), pd, place(p["bt"]), place(torch.tensor(p["lens"], dtype=torch.int32)),
+                                     place(torch.tensor(p["cu"], dtype=torch.int32)))
+    torch.cuda.synchronize()
+    out = whole.cpu()
+    return out[1:P + 1], out[[0, P + 1]]
+
+
+@pytest.mark.parametrize("shift", [False, True], ids=["base0", "base4"])
+@pytest.mark.parametrize("name", ix.APPEND_CASES)
+def test_append_edges(built, dev, name, shift):
+    """The contract of csrc/kv_append_paged_index_bf16.cuh, byte for byte against ix.append_ref, every other pool byte and the guard pages
+    before and after the pool keeping their marker: pages of 32, 128, 256; empty sequences at the start, in the middle and at the end;
+    B = 1 with one row; B = 37 with five sequences that have rows; packed rows in front of cu_q[0] and behind cu_q[B]; seqlens[b] < T_b
+    (pos < 0) and seqlens[b] > Nmax (pos >= Nmax) write nothing; table entries -1 and P under live positions store nothing; cu_q with a
+    negative first entry and a last entry past total_q -- the Python entry passes cu_q to the device unread, so the clamp that runs is the
+    kernel's. base4: block_table, seqlens and cu_q 4 bytes past a 16-byte boundary."""
+    p = ix.append_problem(name)
+    start = torch.full((p["P"], p["page"], ix.D), ix.MARK, dtype=torch.int16).view(BF)
+    want = ix.append_ref(start, p["bt"], p["lens"], p["cu"], p["k_new"])
+    got, guards = _run_append(p, shift)
+    assert bool((guards.view(torch.int16) == ix.MARK).all()), "guard pages of the pool"
+    assert torch.equal(got.view(torch.int16), want.view(torch.int16)), name
+    assert int((got.view(torch.int16) != ix.MARK).any(dim=-1).sum()) > 0
 
 
 # ---------------------------------------------------------------------------------------------------- 5. independence, replay, alignment

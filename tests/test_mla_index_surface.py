@@ -1,7 +1,8 @@
 """CPU: the DSA indexer (include/cln_amd_ext.h: cln_kv_append_paged_index_bf16, cln_mla_index_logits_paged_bf16, cln_mla_index_topk with
 their describe entries; csrc/kv_append_paged_index_bf16.*, csrc/mla_index_logits_paged_bf16.*, csrc/mla_index_topk.*) -- the
 top-k reference against a brute-force definition, the logits reference against the two wrong readings of the ReLU, the exact case's
-partial sums, header, exports and package, every status that returns before a device call in its documented order, the Python entries'
+partial sums, a model of the top-k kernel with named faults against the long rows and the old ones, what the case builders claim (where the
+tie class starts and krem is cut, which blocks hold winners, the row residues, the wraps of the large rows, the append edges), header, exports and package, every status that returns before a device call in its documented order, the Python entries'
 refusals, the describe texts against their manifest mirrors and the kernels' resources in the built library. No GPU needed."""
 import ctypes
 import glob
@@ -51,7 +52,7 @@ def test_topk_reference_is_the_brute_force_definition():
     assert ix.topk_ref(lg, [9], 2).tolist() == [[[4, 5]]] and ix.topk_ref(lg, [2], 4).tolist() == [[[0, 1, -1, -1]]]
 
 
-@pytest.mark.parametrize("case", [("one",) + ht + (16,) for ht in ix.ONE_HT] + [("long",)], ids=lambda c: "-".join(str(x) for x in c))
+@pytest.mark.parametrize("case", [("one",) + ht + (16,) for ht in ix.ONE_HT + ix.ONE_HT_MORE] + [("long",)], ids=lambda c: "-".join(str(x) for x in c))
 def test_the_gpu_cases_would_notice_a_missing_or_a_misplaced_relu(case):
     """For every random-data case of tests/test_gpu_mla_index.py the reference without the ReLU, and with the ReLU applied after the head
     sum, lies more than 20 x the bound from the true reference at some position."""
@@ -67,7 +68,7 @@ def test_the_gpu_cases_would_notice_a_missing_or_a_misplaced_relu(case):
 
 
 def test_exact_case_stays_below_two_to_the_24():
-    for args in ((64, 3, 16), (17, 3, 16)):
+    for args in ((64, 3, 16), (17, 3, 16), (48, 3, 16), (33, 3, 16), (49, 3, 16)):
         q, w, (pool, bt), lens, ld = ix.exact_case(*args)
         _, bound, _ = ix.logits_ref(q, w, pool, bt, lens, ld)
         a = bound / (ix.EPS_TERMS * 2.0 ** -23)  # A = sum_h |w_h| sum_d |q k|: above every partial sum
@@ -84,6 +85,173 @@ def test_pool_builder_poisons_every_unlisted_row():
     assert bool(torch.isfinite(pool[listed].float()).all()) and bool(torch.isnan(pool[~listed].float()).all()) and int((~listed).sum()) > 16
     for b, n in enumerate(lens):
         assert all(bool(torch.isnan(pool[int(p)].float()).all()) for p in bt[b, -(-n // 16):])
+
+
+# ---------------------------------------------------------------------------------------------------- the long rows bite
+
+def _long_rows(block=ix.SCAN_BLOCK, kinds=ix.LONG_KINDS, prod=True):
+    """Every (kind, n, topk, vals, facts) of tests/test_gpu_mla_index_long_rows.py (block = 4096), or their shortened versions."""
+    for kind in kinds:
+        for topk in ix.long_topks(block):
+            for n in ix.long_ns(block) + ([ix.PROD_N] if prod and block == ix.SCAN_BLOCK and topk == 2048 else []):
+                row = ix.long_row(kind, n, topk, block)
+                if row is not None:
+                    yield kind, n, topk, row[0], row[1]
+
+
+def _wrong(vals, topk, want, fault, block=ix.SCAN_BLOCK):
+    got, info = ix.topk_model(vals, topk, fault=fault, block=block)
+    return not torch.equal(got, want) or bool(info["spill"])
+
+
+@pytest.mark.parametrize("kind", ix.LONG_KINDS)
+def test_long_rows_hold_what_their_builders_claim_and_the_model_is_the_reference(kind):
+    """With fault=None the model of the kernel's three steps equals topk_ref on every long row, and every row has the property its recipe
+    states: where the winners lie, where the threshold's tie class starts and where krem is cut, how many blocks the pass runs."""
+    B = ix.SCAN_BLOCK
+    seen = set()
+    for _, n, topk, x, facts in _long_rows(kinds=[kind]):
+        want = ix.topk_row(x, topk)
+        got, info = ix.topk_model(x, topk)
+        assert torch.equal(got, want) and not info["spill"], (kind, n, topk)
+        assert torch.equal(ix.topk_ref(ix.long_logits(kind, n, topk, ld=max(n, ix.LONG_TOPK_LD))[0], [n], topk)[0, 0], want)
+        keys, prefix, krem = info["keys"], info["prefix"], info["krem"]
+        gt, eq = (keys > prefix), (keys == prefix)
+        assert int(gt.sum()) + krem == topk and int(eq.sum()) >= krem
+        cut = int(eq.nonzero()[krem - 1])  # the last tie taken
+        blocks_with_winners = sorted(set((want.long() // B).tolist()))
+        seen.add((n, topk))
+        if "selected" in facts:
+            assert torch.equal(facts["selected"].to(torch.int32), want), (kind, n, topk)
+        if kind == "late":
+            assert int(want.min()) >= facts["from"] and int(want[-1]) == n - 1 and info["blocks"] == info["nblocks"] >= 2
+            assert facts["from"] == (n - 1) // B * B or n - (n - 1) // B * B <= topk  # the last block, unless it is too short for topk
+        elif kind == "early":
+            assert int(want.max()) < facts["to"] and info["blocks"] <= -(-facts["to"] // B) and blocks_with_winners[0] == 0
+            assert (topk <= B and blocks_with_winners == [0]) or (topk > B and blocks_with_winners == [0, 1])
+            assert info["blocks"] < info["nblocks"] or n <= facts["to"]  # the break fires with whole blocks left
+        elif kind == "straddle":
+            first = int(eq.nonzero()[0])
+            assert first < B and bool(eq[3 * B:].any()) and int(eq[:2 * B].sum()) == 2 * facts["e"] < krem  # starts in block 0, runs past 3 B
+            assert 2 * B < cut < 3 * B - 1 and bool(eq[cut + 1:3 * B].any())                         # krem is cut strictly inside block 2
+            assert all(int(gt[b * B:min((b + 1) * B, cut)].sum()) > 0 for b in range(3)) and not bool(gt[3 * B:].any())
+            assert info["blocks"] == 3 < info["nblocks"]
+        elif kind == "spread":
+            full = range(min(info["blocks"], n // B))  # a ragged last block may hold one position
+            assert all(bool(eq[b * B:(b + 1) * B].any()) for b in full)
+            if topk >= 2048 and n < ix.PROD_N:
+                assert all(bool(gt[b * B:(b + 1) * B].any()) for b in full) and info["blocks"] >= 2
+        else:
+            span = B // ix.WAVES
+            p = want.long()
+            cand = (p % span == 0) | (p % span == span - 1) | (p % 4 == 3)
+            assert int(cand.sum()) == min(topk, facts["candidates"]) and (topk < 16 * 2 * info["nblocks"] or blocks_with_winners == list(range(info["nblocks"])))
+    print("%s: %d rows" % (kind, len(seen)))
+    # 2 ... 6 blocks and the production row of 32, topk 4097 and 6000 among them
+    assert {n for n, _ in seen} >= set(ix.long_ns()[4 if kind == "straddle" else 0:]) | {ix.PROD_N} and {4097, 6000} <= {k for _, k in seen}
+
+
+def test_model_is_the_brute_force_definition_on_shortened_long_rows():
+    """The same recipes at a scan block of 256 positions (rows of 511 ... 1281, topk 1 ... 375): the model equals topk_brute."""
+    count = 0
+    for kind, n, topk, x, _ in _long_rows(block=256):
+        got, info = ix.topk_model(x, topk, block=256)
+        assert got.tolist() == ix.topk_brute(x.tolist(), topk), (kind, n, topk)
+        count += 1
+    assert count > 150
+
+
+def test_every_harmful_fault_of_the_model_changes_a_long_row_and_the_old_rows_miss_the_block_faults():
+    """Each named fault of topk_model, on the long rows of tests/test_gpu_mla_index_long_rows.py and on the rows the suite had before
+    (topk_case, n <= 5000: two scan blocks at the most). Every harmful fault changes the list of a long row; the two harmless ones change
+    none anywhere (the break is an optimisation; the slot clip cannot bite on a row that holds still: topk_model's docstring). The old rows
+    see none of the faults that need a third block -- a count buffer used a second time, a pass that ends after two blocks, a carry that
+    forgets the blocks in front of the previous one: the gap the long rows close."""
+    faults = ix.FAULTS_HARMFUL + ix.FAULTS_HARMLESS
+    new = {f: [] for f in faults}
+    for kind, n, topk, x, _ in _long_rows():
+        want = ix.topk_row(x, topk)
+        for f in faults:
+            if _wrong(x, topk, want, f):
+                new[f].append((kind, n, topk))
+    old = {f: 0 for f in faults}
+    rows = 0
+    for x, topk, _ in ix.old_topk_rows():
+        want = ix.topk_row(x, topk)
+        rows += 1
+        for f in faults:
+            old[f] += _wrong(x, topk, want, f)
+    for f in faults:
+        print("fault %-24s wrong on %3d long rows (by kind: %s), on %3d of the %d old rows"
+              % (f, len(new[f]), {k: sum(c[0] == k for c in new[f]) for k in ix.LONG_KINDS}, old[f], rows))
+    assert all(new[f] for f in ix.FAULTS_HARMFUL) and not any(new[f] or old[f] for f in ix.FAULTS_HARMLESS)
+    assert rows >= 100 and old["stale_counts"] == 0 and old["stop_after_two_blocks"] == 0 and old["no_carry_gt"] == 0 and old["no_carry_eq"] == 0
+    assert old["ties_last"] > 0  # the old rows were not blind: what two blocks can show, they showed
+    # every kind but one catches a fault; "early" cannot (its list is complete after block 0 or 1, where the old rows already look): it is
+    # there to take the break with whole blocks left, which no fault of a model can stand for -- the kernel either leaves the loop or hangs
+    assert all(any(c[0] == k for f in ix.FAULTS_HARMFUL for c in new[f]) == (k != "early") for k in ix.LONG_KINDS)
+    assert any(c[0] == "straddle" for c in new["no_carry_eq"]) and any(c[0] == "late" for c in new["stale_counts"])
+    assert any(topk > ix.SCAN_BLOCK for _, _, topk in new["stop_after_two_blocks"])
+
+
+def test_align_rows_start_at_every_residue():
+    """fp32 rows of ld = 4101 or 4103 elements start at 0, 4, 8 and 12 bytes past a 16-byte boundary within six rows; ld = 4102 gives 0 and 8,
+    and 4 and 12 when the tensor itself starts 4 bytes in; the lengths make n = 4097, 4100 and ld occur."""
+    for ld in ix.ALIGN_LDS:
+        res, res4 = set(ix.row_residues(ld)), set(ix.row_residues(ld, base=4))
+        assert res | res4 == {0, 4, 8, 12}
+        assert (res == {0, 4, 8, 12} == res4) if ld % 2 else (res == {0, 8} and res4 == {4, 12})
+        ns = set()
+        for which in (0, 1):
+            x, lens = ix.align_case(ld, "ties", which)
+            vis = ix.visible(lens, ix.ALIGN_T, ld)
+            ns |= {v for row in vis for v in row}
+            for b in range(ix.ALIGN_B):
+                for t in range(ix.ALIGN_T):
+                    assert bool(torch.isnan(x[b, t, vis[b][t]:]).all()) and not bool(torch.isnan(x[b, t, :vis[b][t]]).any())
+        assert {4097, 4100, ld} <= ns, (ld, sorted(ns))
+
+
+def test_large_rows_wrap_into_the_empty_row():
+    """tests/test_gpu_mla_index_large_rows.py: with ld = 2^30 + 1 a row start whose byte offset or element offset wraps at 32 bits lands in
+    the window of row 0, whose sequence is empty; no live row is the image of another."""
+    ld, Nmax = ix.ROWS_LD, ix.ROWS_NMAX
+    assert ix.ROWS_LENS[0] == 0 and 4 * ld > 2 ** 32 and 2 * ld > 2 ** 31 and 4 * ld > 2 ** 32
+    for r in range(1, 5):
+        assert r * ld == r * 2 ** 30 + r
+        for image in ix.row_start_wraps(r):
+            assert image == r * ld or (0 <= image and image + Nmax <= Nmax + 8), (r, image)
+        assert any(image != r * ld for image in ix.row_start_wraps(r))
+    assert ix.row_start_wraps(4)[1] == 4 and ix.row_start_wraps(1) == (1, ld)
+    x, lens = ix.rows_topk_case()
+    for b, n in enumerate(lens):
+        if n > 64:
+            assert ix.topk_row(x[b, 0, :n], 64).tolist() != list(range(64))
+
+
+@pytest.mark.parametrize("name", ix.APPEND_CASES)
+def test_append_problems_are_the_edges_they_claim(name):
+    p = ix.append_problem(name)
+    page, P, bt, lens, cu, k_new, new = (p[k] for k in ("page", "P", "bt", "lens", "cu", "k_new", "new"))
+    c, Ts = ix.append_clamped(cu, k_new.shape[0])
+    assert Ts == new and c[0] >= 0 and c[-1] <= k_new.shape[0]
+    Nmax = bt.shape[1] * page
+    pool = torch.full((P, page, ix.D), 0, dtype=torch.int16).fill_(ix.MARK).view(BF)
+    want = ix.append_ref(pool, bt, lens, cu, k_new)
+    written = int((want.view(torch.int16) != pool.view(torch.int16)).any(dim=-1).sum())
+    live = sum(1 for b, t in enumerate(Ts) for i in range(t)
+               if 0 <= lens[b] - t + i < Nmax and 0 <= int(bt[b, (lens[b] - t + i) // page]) < P)
+    assert written == live > 0
+    dropped = sum(Ts) - live
+    assert (dropped > 0) == (name in ("short_len", "past_nmax", "bad_entries")), (name, dropped)
+    if name == "empties":
+        assert new == [0, 3, 0, 0, 20, 0]
+    if name == "cu_outside":
+        assert cu[0] < 0 and cu[-1] > k_new.shape[0]
+    if name == "bad_entries":
+        assert sorted(int(v) for v in bt.flatten() if not 0 <= int(v) < P) == [-1, P]
+    if name == "b37":
+        assert len(new) == 37 and sum(t > 0 for t in new) == 5
 
 
 # ---------------------------------------------------------------------------------------------------- header, exports

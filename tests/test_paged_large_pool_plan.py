@@ -11,12 +11,25 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import paged_large_pool as lp  # noqa: E402
 
 N_LIVE = (15, 20, 256)  # the attention cases, the append cases, the several-splits cases of tests/test_gpu_paged_large_pool.py
+INDEX_N_LIVE = (13, 40, 404)  # the append problem, one_case(17, 3, 16) and long_case() of tests/test_gpu_mla_index_large_pool.py
 GEOMETRIES = [(Hkv, D, s) for Hkv in (2, 1) for D in lp.DS for s in (2, 1)]  # Hkv = 1: the several-splits cases
 
 
 @pytest.mark.parametrize("n_live", N_LIVE)
 @pytest.mark.parametrize("Hkv,D,s", GEOMETRIES)
 def test_named_pages_cross_the_boundaries_and_every_wrap_lands_on_poison(Hkv, D, s, n_live):
+    _check(Hkv, D, s, n_live)
+
+
+@pytest.mark.parametrize("n_live", INDEX_N_LIVE)
+def test_the_plan_holds_for_the_index_key_pool(n_live):
+    """The DSA indexer's pool [P, 16, 128] in bf16 (tests/test_gpu_mla_index_large_pool.py): E = 2048, s = 2, the geometry of Hkv = 2, D = 64
+    above, at the page counts of its cases; P = 2^21 + 16, and the view ends within 16 pages past element 2^32."""
+    assert lp.page_elems(64, 2) == 16 * 128 and lp.pages(2048, 2) == 2 ** 21 + 16
+    _check(2, 64, 2, n_live)
+
+
+def _check(Hkv, D, s, n_live):
     E = lp.page_elems(D, Hkv)
     p = lp.plan(E, s, n_live, seed=n_live)
     P, named, poison = p["P"], p["named"], set(p["poison"])
