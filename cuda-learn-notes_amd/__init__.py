@@ -564,6 +564,32 @@ def mla_index_topk(logits, seqlens, topk, indices):
     return host.mla_index_topk(logits, seqlens, topk, indices)
 
 
+def index_pool_fp8_views(idx_pool):
+    """(codes, scales) of an FP8 index pool torch.uint8 [P,page,132]: codes float8_e4m3fn [P,page,128] (slot r at byte 128 * r of its page) and
+    scales float32 [P,page] (at byte 128 * page + 4 * r), views of the same storage, no copy; value = e4m3(code) * scale. Not a reference
+    name."""
+    from . import host
+    return host.index_pool_fp8_views(idx_pool)
+
+
+def kv_append_paged_index_bf16_fp8(k_idx_new, idx_pool, block_table, seqlens, cu_q, scale_pow2=False):
+    """kv_append_paged_index_bf16 into an index-key cache held in FP8 with one fp32 scale per token (DeepSeek-V3.2's own format, 132 bytes a
+    token): idx_pool uint8 [P,page,132] in the layout of index_pool_fp8_views; per live token scale = max(amax, 1e-4) / 448 in fp32, rounded up
+    to a power of two with scale_pow2 (ue8m0), code = e4m3fn(clamp(k / scale, ±448)); every other byte keeps its value. C entry
+    cln_kv_append_paged_index_bf16_fp8 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.kv_append_paged_index_bf16_fp8(k_idx_new, idx_pool, block_table, seqlens, cu_q, scale_pow2)
+
+
+def mla_index_logits_paged_bf16_fp8(q_idx, weights, idx_pool, block_table, seqlens, logits):
+    """mla_index_logits_paged_bf16 over the FP8 index pool uint8 [P,page,132]: logits[b,t,j] = s_j * sum_h weights[b,t,h] *
+    max(0, q_idx[b,t,h] . c_j) for 0 <= j < vis(b,t), c_j the codes read as numbers and s_j the token's scale (finite and >= 0), nothing else
+    written or read; q_idx bf16, weights and logits fp32, any T >= 1, Hi in 1 … 64. C entry cln_mla_index_logits_paged_bf16_fp8
+    (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.mla_index_logits_paged_bf16_fp8(q_idx, weights, idx_pool, block_table, seqlens, logits)
+
+
 def fa2_decode_paged_mla_sparse_bf16_fp8(q, pool, block_table, seqlens, kv_scale, indices, softmax_scale, out, lse=None, workspace=None):
     """fa2_decode_paged_mla_sparse_bf16 over a latent cache held in FP8 (a DeepSeek-V3.2 step on the pool kv_append_paged_mla_bf16_fp8 writes):
     pool torch.float8_e4m3fn [P,page,576] of rows [c 512 | k_pe 64] in codes, kv_scale fp32 [1] on the GPU (one scale for the whole pool: value

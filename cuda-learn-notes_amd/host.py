@@ -1851,3 +1851,99 @@ def mla_index_topk(logits, seqlens, topk, indices):
     _check_shape(indices, B, T, topk)
     rc = fn(logits.data_ptr(), seqlens.data_ptr(), indices.data_ptr(), B, T, ld, topk, _stream())
     _raise(name, rc, "%s: ld, B * T or topk * B * T too large for one launch" % name)
+
+
+# ---- the indexer's cache held in FP8 with one fp32 scale per token: the model's own format, 132 bytes a token. The pool is
+# bytes [P,page,132]; inside a page the 128 * page code bytes come first and the page's fp32 scales behind them
+_IDX_FP8_ROW = 132
+
+
+def index_pool_fp8_views(idx_pool):
+    """(codes, scales) of an FP8 index pool, torch.uint8 [P,page,132] contiguous and 16-byte aligned: codes torch.float8_e4m3fn [P,page,128]
+    (token slot r of page p at byte 128 * r of the page) and scales torch.float32 [P,page] (at byte 128 * page + 4 * r), both views of the
+    pool's own storage, no copy. A stored token means k_d = e4m3(code_d) * scale. Works on any device."""
+    _check_dtype(idx_pool, torch.uint8)
+    if idx_pool.dim() != 3 or idx_pool.shape[2] != _IDX_FP8_ROW or not idx_pool.is_contiguous() or idx_pool.data_ptr() % 16:
+        raise RuntimeError("Tensor size mismatch!")
+    P, page, _ = idx_pool.shape
+    if page not in _PAGED_PAGES:
+        raise _paged_page_error("index_pool_fp8_views", page)
+    pages = idx_pool.view(P, page * _IDX_FP8_ROW)
+    codes = pages[:, :page * _IDX_DIM].view(torch.float8_e4m3fn).view(P, page, _IDX_DIM)
+    scales = pages[:, page * _IDX_DIM:].view(torch.float32)
+    return codes, scales
+
+
+def _index_pool_fp8(name, idx_pool):
+    """(P, page) of an FP8 index pool, or the refusal: uint8, [P,page,132], a supported page."""
+    _check_dtype(idx_pool, torch.uint8)
+    if idx_pool.dim() != 3:
+        raise RuntimeError("Tensor size mismatch!")
+    P, page, _ = idx_pool.shape
+    _check_shape(idx_pool, P, page, _IDX_FP8_ROW)
+    return P, page
+
+
+def kv_append_paged_index_bf16_fp8(k_idx_new, idx_pool, block_table, seqlens, cu_q, scale_pow2=False):
+    """kv_append_paged_index_bf16 into an index-key cache held in FP8 with one fp32 scale per token; one launch. k_idx_new torch.bfloat16
+    [total_q,128]; idx_pool torch.uint8 [P,page,132], contiguous, written in place (the layout: index_pool_fp8_views); block_table, seqlens
+    (the lengths AFTER the append) and cu_q, the packed convention, liveness and the untouched rows of no sequence as there. Per live token,
+    in IEEE fp32: a = max(amax |k|, 1e-4), scale = a / 448, with scale_pow2 rounded up to a power of two (ue8m0: the model's configuration),
+    code = e4m3fn(clamp(k * (1 / scale), ±448)), round to nearest even; every pool byte that is not a live token's 128 codes or 4 scale bytes
+    keeps its value. Inputs are finite: the caller's contract. Deterministic. C entry cln_kv_append_paged_index_bf16_fp8
+    (include/cln_amd_ext.h); no CPU path."""
+    name = "kv_append_paged_index_bf16_fp8"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 6 + [ctypes.c_void_p])
+    _decode_check((k_idx_new,), (block_table, seqlens, cu_q), torch.bfloat16)
+    P, page = _index_pool_fp8(name, idx_pool)
+    _check_dev(idx_pool)
+    if k_idx_new.dim() != 2 or block_table.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    total_q = k_idx_new.shape[0]
+    B, max_pages = block_table.shape
+    _check_shape(k_idx_new, total_q, _IDX_DIM)
+    _check_shape(seqlens, B)
+    _check_shape(cu_q, B + 1)
+    if page not in _PAGED_PAGES:
+        raise _paged_page_error(name, page)
+    rc = fn(k_idx_new.data_ptr(), idx_pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), cu_q.data_ptr(), B, total_q, P, max_pages,
+            page, 1 if scale_pow2 else 0, _stream())
+    _raise(name, rc, "%s: max_pages * page too large for one launch" % name)
+
+
+def mla_index_logits_paged_bf16_fp8(q_idx, weights, idx_pool, block_table, seqlens, logits):
+    """mla_index_logits_paged_bf16 over an index-key cache held in FP8 with one fp32 scale per token; one launch, no workspace. q_idx
+    torch.bfloat16 [B,T,Hi,128]; weights fp32 [B,T,Hi]; idx_pool torch.uint8 [P,page,132] (the layout: index_pool_fp8_views); block_table
+    int32 [B,max_pages]; seqlens int32 [B]; logits fp32 [B,T,ld], contiguous. With c_j the codes of position j read as numbers and s_j its
+    scale, writes logits[b,t,j] = s_j * sum_h weights[b,t,h] * max(0, q_idx[b,t,h] . c_j) for 0 <= j < vis(b,t) and nothing else; cap, vis and
+    what is never read are the bf16 entry's. The scale multiplies once per key after the head sum, in fp32: the dequantise-then-ReLU form
+    exactly for s_j >= 0 (s_j finite and >= 0 and no NaN code, 0x7F or 0xFF, in a visible row: the caller's contract, not checked; the append
+    writes a scale > 0 and, for finite keys, no NaN code). Any T >= 1, Hi in 1 … 64. The codes become bf16
+    exactly on the way into the matrix operand; fp32 accumulation, a fixed order: deterministic, and a sequence's bits do not depend on its
+    neighbours. C entry cln_mla_index_logits_paged_bf16_fp8 (include/cln_amd_ext.h); no CPU path."""
+    name = "mla_index_logits_paged_bf16_fp8"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 3 + [ctypes.c_longlong] + [ctypes.c_int] * 3 + [ctypes.c_void_p])
+    _decode_check((q_idx,), (block_table, seqlens), torch.bfloat16)
+    for t in (weights, logits):
+        _check_dtype(t, torch.float32)
+    P, page = _index_pool_fp8(name, idx_pool)
+    _check_dev(idx_pool, weights, logits)
+    if q_idx.dim() != 4 or block_table.dim() != 2 or logits.dim() != 3:
+        raise RuntimeError("Tensor size mismatch!")
+    B, T, Hi, D = q_idx.shape
+    ld = logits.shape[2]
+    if D != _IDX_DIM:
+        raise RuntimeError("%s: q_idx of %d dims not supported (%d)" % (name, D, _IDX_DIM))
+    if block_table.shape[0] != B:
+        raise RuntimeError("Tensor size mismatch!")
+    max_pages = block_table.shape[1]
+    _check_shape(weights, B, T, Hi)
+    _check_shape(seqlens, B)
+    _check_shape(logits, B, T, ld)
+    if Hi > _IDX_MAX_HEADS:
+        raise RuntimeError("%s: %d index heads not supported (1 … %d)" % (name, Hi, _IDX_MAX_HEADS))
+    if page not in _PAGED_PAGES:
+        raise _paged_page_error(name, page)
+    rc = fn(q_idx.data_ptr(), weights.data_ptr(), idx_pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), logits.data_ptr(), B, T, Hi,
+            ld, P, max_pages, page, _stream())
+    _raise(name, rc, "%s: max_pages * page, B * T or B * T * ceil(cap / 1024) too large for one launch" % name)

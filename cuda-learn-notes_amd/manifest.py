@@ -851,3 +851,18 @@ def describe_mla_index_topk(B, T, ld, topk):
     import ctypes
     i, ll = ctypes.c_int, ctypes.c_longlong
     return _describe_index("cln_mla_index_topk", [i, i, ll, i], tuple(int(x) for x in (B, T, ld, topk)))
+
+
+def describe_kv_append_paged_index_bf16_fp8(B, total_q, max_pages, page, scale_pow2=False):
+    """describe() for cln_kv_append_paged_index_bf16_fp8 (include/cln_amd_ext.h): the kernel, the launch, the page layout and the
+    per-token quantiser as text (no GPU needed). ValueError for an unsupported or invalid shape."""
+    return _describe_bf16("cln_kv_append_paged_index_bf16_fp8", tuple(int(x) for x in (B, total_q, max_pages, page, scale_pow2)), 2048)
+
+
+def describe_mla_index_logits_paged_bf16_fp8(B, T, Hi, ld, max_pages, page):
+    """describe() for cln_mla_index_logits_paged_bf16_fp8 (include/cln_amd_ext.h): the kernel instantiation, the jobs, the page
+    layout, the loader, the conversion, the MFMA count and where the scale enters as text (no GPU needed). ValueError for an unsupported or
+    invalid shape."""
+    import ctypes
+    i, ll = ctypes.c_int, ctypes.c_longlong
+    return _describe_index("cln_mla_index_logits_paged_bf16_fp8", [i, i, i, ll, i, i], tuple(int(x) for x in (B, T, Hi, ld, max_pages, page)), 4096)

@@ -706,6 +706,42 @@ int cln_fa2_decode_paged_mla_sparse_bf16_fp8(const void* q, const void* pool, co
 int cln_fa2_decode_paged_mla_sparse_bf16_fp8_describe(int B, int T, int Hq, int topk, int max_pages, int page, float softmax_scale, char* buf,
                                                       int len);
 
+/* ---- The indexer's cache held in FP8 (OCP e4m3fn) with one fp32 scale per token: DeepSeek-V3.2's own format for
+ * its index keys, 132 bytes a token where the bf16 pool stores 256. idx_pool is BYTES, [P, page, 132] to the caller, 16-byte aligned, behind the
+ * block table and the lengths of the latent cache. Inside a page of 132 page bytes:
+ *     bytes [0, 128 page)          codes  [page, 128] e4m3fn, token slot r at byte 128 r
+ *     bytes [128 page, 132 page)   scales [page] fp32,        token slot r at byte 128 page + 4 r
+ * (132 page is a multiple of 16 for every supported page, 16 ... 256: a code row is 16-byte aligned, a scale 4-byte aligned.) A stored token
+ * means k_d = e4m3(code_d) scale. The layout as written here is the contract. cln_mla_index_topk and both sparse decodes take the results as
+ * they are; nothing above changes.
+ *
+ * cln_kv_append_paged_index_bf16_fp8: cln_kv_append_paged_index_bf16 with a quantising store. Which row goes where is that entry's, word for
+ * word (packed rows by cu_q clamped on the device, seqlens AFTER the append, liveness, a table entry outside [0, P) stores nothing, rows of no
+ * sequence untouched); every byte of the pool that is not a live token's 128 codes or 4 scale bytes keeps its value. Per live token, all in
+ * IEEE fp32: a = max(max_d |k_d|, 1e-4f); scale = a / 448.0f; if scale_pow2, scale = the smallest power of two >= scale (on the bits: mantissa
+ * zero -> unchanged, else exponent + 1 and mantissa 0); inv = 1.0f / scale; code_d = e4m3fn, round to nearest even, of clamp(k_d inv, -448,
+ * 448); the scale is stored as computed (always > 0). Inputs are finite: the caller's contract. scale_pow2 is 0 or 1; the model's
+ * configuration uses 1 (ue8m0). Status, in this order: a missing or misaligned pointer (k_idx_new, idx_pool 16 bytes; the int arrays 4) or
+ * idx_pool equal to an input (-1); P <= 0 (-1); scale_pow2 neither 0 nor 1 (-1); a non-positive B, total_q, max_pages or page (-1); another
+ * page or max_pages page >= 2^31 (-2). _describe: buf / len (-1), scale_pow2 (-1), then the shape.
+ *
+ * cln_mla_index_logits_paged_bf16_fp8: cln_mla_index_logits_paged_bf16's argument list with this pool in place of the bf16 one; q_idx bf16
+ * [B,T,Hi,128], weights fp32 [B,T,Hi], logits fp32 [B,T,ld]. With c_j the codes of position j read as numbers and s_j its scale it writes
+ *     logits[b,t,j] = s_j sum_h weights[b,t,h] max(0, q_idx[b,t,h] . c_j)        for 0 <= j < vis(b,t)
+ * and NOTHING ELSE; cap, vis and "no key, scale or table entry at or past vis is read" are the bf16 entry's rules. The scale is multiplied
+ * once per key, after the head sum, in fp32: equal to the dequantise-then-ReLU form exactly for s_j >= 0. s_j finite and >= 0 and no NaN code
+ * in a visible row are the caller's contract (what the append writes is > 0 and never NaN). The codes are converted to bf16 exactly on the
+ * way into the matrix operand, so the products are exact in fp32; the order of operations depends on neither the grid, the batch nor the
+ * length. Any T >= 1, Hi in 1 ... 64, no workspace. Status and order: cln_mla_index_logits_paged_bf16's.
+ */
+int cln_kv_append_paged_index_bf16_fp8(const void* k_idx_new, void* idx_pool, const int* block_table, const int* seqlens, const int* cu_q, int B,
+                                       int total_q, int P, int max_pages, int page, int scale_pow2, void* stream);
+int cln_kv_append_paged_index_bf16_fp8_describe(int B, int total_q, int max_pages, int page, int scale_pow2, char* buf, int len);
+int cln_mla_index_logits_paged_bf16_fp8(const void* q_idx, const float* weights, const void* idx_pool, const int* block_table,
+                                        const int* seqlens, float* logits, int B, int T, int Hi, long long ld, int P, int max_pages, int page,
+                                        void* stream);
+int cln_mla_index_logits_paged_bf16_fp8_describe(int B, int T, int Hi, long long ld, int max_pages, int page, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
