@@ -1,7 +1,7 @@
 // Compile unit of the bf16 sliding-window multi-token paged decode attention entries cln_fa2_decode_paged_multi_window_bf16_plan /
 // cln_fa2_decode_paged_multi_window_bf16 / cln_fa2_decode_paged_multi_window_bf16_describe (include/cln_amd_ext.h; kernels:
-// flash_attn_decode_paged_multi_window_bf16.cuh). The plan is paged::multi_window_plan; the checks and the status codes are those of
-// flash_attn_decode_paged_multi_bf16.hip, then window <= 0 -> -1.
+// flash_attn_decode_paged_multi_window_bf16.cuh): bf16 pools, G a power of two, no sinks. The plan, the checks, their order and the text are
+// paged::window_plan_entry / window_decode / window_decode_describe (paged_entry.h).
 #include "flash_attn_decode_paged_multi_window_bf16.cuh"
 #include "paged_entry.h"
 
@@ -9,50 +9,24 @@ static_assert(fa2b::kMultiKeyStep == fa2pm::kKeyStep, "paged::multi_window_plan 
 
 CLN_API int cln_fa2_decode_paged_multi_window_bf16_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window, int* splits,
                                                         int* chunk, long long* workspace_bytes) {
-  fa2d::PagedGeometry g;
-  fa2d::Plan p;
-  return fa2d::plan_out(paged::multi_window_plan(B, T, Hq, Hkv, max_pages, page, D, window, &g, &p), p, splits, chunk, workspace_bytes);
+  return paged::window_plan_entry<paged::kPow2G>({B, T, Hq, Hkv, max_pages, page, D, window}, splits, chunk, workspace_bytes);
 }
 
 CLN_API int cln_fa2_decode_paged_multi_window_bf16(const void* q, const void* k_pages, const void* v_pages, const int* block_table,
                                                    const int* seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B, int T,
                                                    int Hq, int Hkv, int P, int max_pages, int page, int D, int window, void* stream) {
-  const void* in[] = {q, k_pages, v_pages, block_table, seqlens};
-  fa2d::PagedGeometry g;
-  fa2d::Plan p = {};
-  const int rc = paged::decode_args(in, 5, {o, lse, workspace}, workspace_bytes, P,
-                                    paged::multi_window_plan(B, T, Hq, Hkv, max_pages, page, D, window, &g, &p), p);
-  if (rc != CLN_OK) return rc;
-  const fa2b::PagedKV kv = {(const bf16_t*)k_pages, (const bf16_t*)v_pages, block_table, Hkv, max_pages, g.page_shift};
+  const void* const in[] = {q, k_pages, v_pages, block_table, seqlens};
   const hipStream_t s = (hipStream_t)stream;
-  return paged::for_head_dim(D, [&](auto d) {
-    return paged::for_row_tiles(paged::multi_tiles(T, g), [&](auto mt) {
-      return fa2b::launch_decode_paged_multi_window<d(), mt()>(q, kv, seqlens, o, lse, workspace, B, T, g.g_shift, p.splits, p.chunk, window, s);
-    });
-  });
+  return paged::window_decode<fa2b::PagedKV, paged::kPow2G>(
+      in, 5, o, lse, workspace, workspace_bytes, P, {B, T, Hq, Hkv, max_pages, page, D, window},
+      [&](auto d, auto mt, auto, const fa2b::PagedKV& kv, const paged::WindowLaunch& w) {
+        return fa2b::launch_decode_paged_multi_window<d(), mt()>(q, kv, seqlens, o, lse, workspace, B, T, w.g.g_shift, w.p.splits, w.p.chunk, window,
+                                                                 s);
+      });
 }
 
 CLN_API int cln_fa2_decode_paged_multi_window_bf16_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D, int window, char* buf,
                                                             int len) {
-  if (!buf || len <= 0) return CLN_ERR_BAD_ARG;
-  fa2d::PagedGeometry g;
-  fa2d::Plan p;
-  const int rc = paged::multi_window_plan(B, T, Hq, Hkv, max_pages, page, D, window, &g, &p);
-  if (rc != CLN_OK) return rc;
-  const int tiles = paged::multi_tiles(T, g);
-  int n = snprintf(buf, len,
-                   "fa2_decode_paged_multi_window_bf16_mfma<D=%d,MT=%d> T=%d G=%d W=%d span=%lld S=%d C=%d page=%d: the S splits of C keys divide the "
-                   "span from base = align_down(max(0, len - T - W + 1), %lld) on, no table entry and no row below base; 4 waves split the %d-key "
-                   "steps, K rows through the block table straight to MFMA fragments, V rows through a transposed LDS read, each row loaded once "
-                   "for the %d query rows (T x G, %d tiles of 16) of its KV head, S^T = K Q^T and O^T = V^T P^T on v_mfma_f32_16x16x32_bf16, fp32 "
-                   "scores, window and causal mask by select, online softmax",
-                   D, tiles, T, g.group, window, paged::multi_window_span(T, page, window, g.Nmax), p.splits, p.chunk, page,
-                   paged::multi_window_unit(page), fa2b::kMultiKeyStep, T * g.group, tiles);
-  if (p.splits > 1 && n < len)
-    n += snprintf(buf + n, len - n,
-                  "; then fa2_decode_combine_window_bf16_rows<D=%d> merges the live splits ceil((len - base) / C) of a query row by log-sum-exp in "
-                  "ascending order (workspace %lld bytes)",
-                  D, p.ws_bytes);
-  if (n < len) n += snprintf(buf + n, len - n, "; deterministic");
-  return n < len ? n : len - 1;
+  return paged::window_decode_describe<fa2b::PagedKV, paged::kPow2G>("fa2_decode_paged_multi_window_bf16_mfma", paged::kNoSinks,
+                                                                     {B, T, Hq, Hkv, max_pages, page, D, window}, buf, len);
 }

@@ -2,24 +2,17 @@
 // G = Hq / Hkv in 1 ... 16, a softmax scale of the caller's and optional logit soft-capping:
 // cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_plan / cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8 /
 // cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_describe (include/cln_amd_ext.h; kernel:
-// flash_attn_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8.cuh). The plan takes neither float and is paged::multi_window_plan_anyg
-// unchanged. The two floats stand behind `window` and are checked first, before any pointer is looked at (paged::softcap_arg); every other check
-// and status code is that of flash_attn_decode_paged_multi_window_sink_anyg_bf16_fp8.hip, argument by argument. softcap == 0 launches the
-// CAP = false instantiations.
+// flash_attn_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8.cuh): the any-G FP8 entry with the two floats behind `window`, checked first;
+// the plan takes neither float and is the any-G entry's. softcap == 0 launches the CAP = false instantiations. The checks, their order and the
+// text are paged::window_decode / softcap_describe_then / window_decode_describe (paged_entry.h).
 #include "flash_attn_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8.cuh"
 #include "paged_entry.h"
 
 static_assert(fa2b::kMultiKeyStep == fa2pm::kKeyStep, "paged::multi_window_plan_anyg plans with the key step of this kernel");
-static_assert(paged::kMaxRowsAnyG == 4 * 16, "paged::for_row_tiles has 1 ... 4 row tiles of 16");
-
-CLN_API int cln_fa2_decode_paged_multi_window_sink_anyg_bf16_fp8_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D,
-                                                                          int window, char* buf, int len);
 
 CLN_API int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D,
                                                                               int window, int* splits, int* chunk, long long* workspace_bytes) {
-  fa2d::PagedGeometry g;
-  fa2d::Plan p;
-  return fa2d::plan_out(paged::multi_window_plan_anyg(B, T, Hq, Hkv, max_pages, page, D, window, &g, &p), p, splits, chunk, workspace_bytes);
+  return paged::window_plan_entry<paged::kAnyG>({B, T, Hq, Hkv, max_pages, page, D, window}, splits, chunk, workspace_bytes);
 }
 
 CLN_API int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8(const void* q, const void* k_pages, const void* v_pages,
@@ -28,37 +21,22 @@ CLN_API int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8(const v
                                                                          void* workspace, long long workspace_bytes, int B, int T, int Hq, int Hkv,
                                                                          int P, int max_pages, int page, int D, int window, float softmax_scale,
                                                                          float softcap, void* stream) {
-  paged::SoftCap sc;
-  int rc = paged::softcap_arg(softmax_scale, softcap, D, &sc);
-  if (rc != CLN_OK) return rc;
-  const void* in[] = {q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, sinks};  // the last five: 4-byte aligned; sinks only when given
-  fa2d::PagedGeometry g;
-  fa2d::Plan p = {};
-  rc = paged::decode_args(in, sinks ? 8 : 7, {o, lse, workspace}, workspace_bytes, P,
-                          paged::multi_window_plan_anyg(B, T, Hq, Hkv, max_pages, page, D, window, &g, &p), p);
-  if (rc != CLN_OK) return rc;
-  const fa2d::PagedKV8 kv = {(const uint8_t*)k_pages, (const uint8_t*)v_pages, k_scale, v_scale, block_table, Hkv, max_pages, g.page_shift};
+  const void* const in[] = {q, k_pages, v_pages, block_table, seqlens, k_scale, v_scale, sinks};
   const hipStream_t s = (hipStream_t)stream;
-  return paged::for_head_dim(D, [&](auto d) {
-    return paged::for_row_tiles(paged::multi_tiles(T, g), [&](auto mt) {
-      if (sc.cap)
-        return fa2b::launch_decode_paged_multi_window_sink_softcap_anyg_fp8<d(), mt(), true>(q, kv, seqlens, sinks, o, lse, workspace, B, T, g.group,
-                                                                                             p.splits, p.chunk, window, sc.mult, sc.pre, sc.cap2, s);
-      return fa2b::launch_decode_paged_multi_window_sink_softcap_anyg_fp8<d(), mt(), false>(q, kv, seqlens, sinks, o, lse, workspace, B, T, g.group,
-                                                                                            p.splits, p.chunk, window, sc.mult, 0.0f, 0.0f, s);
-    });
-  });
+  return paged::window_decode<fa2d::PagedKV8, paged::kAnyG>(
+      in, sinks ? 8 : 7, o, lse, workspace, workspace_bytes, P, {B, T, Hq, Hkv, max_pages, page, D, window, softmax_scale, softcap},
+      [&](auto d, auto mt, auto cap, const fa2d::PagedKV8& kv, const paged::WindowLaunch& w) {
+        return fa2b::launch_decode_paged_multi_window_sink_softcap_anyg_fp8<d(), mt(), cap()>(
+            q, kv, seqlens, sinks, o, lse, workspace, B, T, w.g.group, w.p.splits, w.p.chunk, window, w.sc.mult, w.sc.pre, w.sc.cap2, s);
+      });
 }
 
 CLN_API int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D,
                                                                                   int window, float softmax_scale, float softcap, char* buf,
                                                                                   int len) {
-  if (!buf || len <= 0) return CLN_ERR_BAD_ARG;
-  paged::SoftCap sc;
-  int rc = paged::softcap_arg(softmax_scale, softcap, D, &sc);
-  if (rc != CLN_OK) return rc;
-  const int n =
-      paged::softcap_describe(buf, len, "fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_mfma", D, softmax_scale, softcap, sc, true);
-  rc = cln_fa2_decode_paged_multi_window_sink_anyg_bf16_fp8_describe(B, T, Hq, Hkv, max_pages, page, D, window, buf + n, len - n);
-  return rc < 0 ? rc : n + rc;
+  const paged::WindowArgs a = {B, T, Hq, Hkv, max_pages, page, D, window, softmax_scale, softcap};
+  return paged::softcap_describe_then(buf, len, "fa2_decode_paged_multi_window_sink_softcap_anyg_bf16_fp8_mfma", a, true, [&](char* rest, int n) {
+    return paged::window_decode_describe<fa2d::PagedKV8, paged::kAnyG>("fa2_decode_paged_multi_window_sink_anyg_bf16_fp8_mfma",
+                                                                       paged::kSinksOptional, a, rest, n);
+  });
 }

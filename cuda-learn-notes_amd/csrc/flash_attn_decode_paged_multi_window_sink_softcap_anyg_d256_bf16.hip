@@ -1,20 +1,18 @@
 // Compile unit of the bf16 multi-token paged decode attention entries at head dim 256 (sliding window, attention sinks, any group size
 // G = Hq / Hkv in 1 ... 16, softmax scale, logit soft-capping): cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_plan /
 // cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16 / cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_describe
-// (include/cln_amd_ext.h; kernel: flash_attn_decode_paged_multi_window_sink_softcap_anyg_d256_bf16.cuh). The plan is this kernel's
-// own: paged::multi_window_plan_anyg_d256, fa2d::split_plan on the 64-key step and D = 256. The argument list, the checking order and the status
-// codes are those of flash_attn_decode_paged_multi_window_sink_softcap_anyg_bf16.hip; D = 256 only, T in 1 ... 8 with T G <= 32.
+// (include/cln_amd_ext.h; kernel: flash_attn_decode_paged_multi_window_sink_softcap_anyg_d256_bf16.cuh): the bf16 softcap entry at
+// D = 256 and no other head dim, T in 1 ... 8 with T G <= 32. The plan is this kernel's own: paged::multi_window_plan_anyg_d256, fa2d::split_plan
+// on the 64-key step and D = 256. The plan entry, the checks and their order are paged::window_plan_entry / window_decode (paged_entry.h); the
+// text is this unit's own: its head names MT, and its LDS and MFMA clauses have no counterpart in the siblings' text.
 #include "flash_attn_decode_paged_multi_window_sink_softcap_anyg_d256_bf16.cuh"
 #include "paged_entry.h"
 
 static_assert(fa2b::kKeyStep256 == paged::kKeyStepD256, "paged::multi_window_plan_anyg_d256 plans with the key step of this kernel");
-static_assert(paged::kMaxRowsD256 == 2 * 16, "paged::for_row_tiles_d256 has 1 or 2 row tiles of 16");
 
 CLN_API int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_plan(int B, int T, int Hq, int Hkv, int max_pages, int page, int D,
                                                                                int window, int* splits, int* chunk, long long* workspace_bytes) {
-  fa2d::PagedGeometry g;
-  fa2d::Plan p;
-  return fa2d::plan_out(paged::multi_window_plan_anyg_d256(B, T, Hq, Hkv, max_pages, page, D, window, &g, &p), p, splits, chunk, workspace_bytes);
+  return paged::window_plan_entry<paged::kAnyGD256>({B, T, Hq, Hkv, max_pages, page, D, window}, splits, chunk, workspace_bytes);
 }
 
 CLN_API int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16(const void* q, const void* k_pages, const void* v_pages,
@@ -22,24 +20,14 @@ CLN_API int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16(const 
                                                                           float* lse, void* workspace, long long workspace_bytes, int B, int T,
                                                                           int Hq, int Hkv, int P, int max_pages, int page, int D, int window,
                                                                           float softmax_scale, float softcap, void* stream) {
-  paged::SoftCap sc;
-  int rc = paged::softcap_arg(softmax_scale, softcap, D, &sc);
-  if (rc != CLN_OK) return rc;
-  const void* in[] = {q, k_pages, v_pages, block_table, seqlens, sinks};  // the last three: 4-byte aligned; sinks only when given
-  fa2d::PagedGeometry g;
-  fa2d::Plan p = {};
-  rc = paged::decode_args(in, sinks ? 6 : 5, {o, lse, workspace}, workspace_bytes, P,
-                          paged::multi_window_plan_anyg_d256(B, T, Hq, Hkv, max_pages, page, D, window, &g, &p), p);
-  if (rc != CLN_OK) return rc;
-  const fa2b::PagedKV kv = {(const bf16_t*)k_pages, (const bf16_t*)v_pages, block_table, Hkv, max_pages, g.page_shift};
+  const void* const in[] = {q, k_pages, v_pages, block_table, seqlens, sinks};
   const hipStream_t s = (hipStream_t)stream;
-  return paged::for_row_tiles_d256(paged::multi_tiles(T, g), [&](auto mt) {
-    if (sc.cap)
-      return fa2b::launch_decode_paged_multi_window_sink_softcap_anyg_d256<mt(), true>(q, kv, seqlens, sinks, o, lse, workspace, B, T, g.group,
-                                                                                       p.splits, p.chunk, window, sc.mult, sc.pre, sc.cap2, s);
-    return fa2b::launch_decode_paged_multi_window_sink_softcap_anyg_d256<mt(), false>(q, kv, seqlens, sinks, o, lse, workspace, B, T, g.group,
-                                                                                      p.splits, p.chunk, window, sc.mult, 0.0f, 0.0f, s);
-  });
+  return paged::window_decode<fa2b::PagedKV, paged::kAnyGD256>(
+      in, sinks ? 6 : 5, o, lse, workspace, workspace_bytes, P, {B, T, Hq, Hkv, max_pages, page, D, window, softmax_scale, softcap},
+      [&](auto, auto mt, auto cap, const fa2b::PagedKV& kv, const paged::WindowLaunch& w) {
+        return fa2b::launch_decode_paged_multi_window_sink_softcap_anyg_d256<mt(), cap()>(
+            q, kv, seqlens, sinks, o, lse, workspace, B, T, w.g.group, w.p.splits, w.p.chunk, window, w.sc.mult, w.sc.pre, w.sc.cap2, s);
+      });
 }
 
 CLN_API int cln_fa2_decode_paged_multi_window_sink_softcap_anyg_d256_bf16_describe(int B, int T, int Hq, int Hkv, int max_pages, int page, int D,

@@ -1,9 +1,9 @@
 // Compile unit of the bf16 packed paged prefill attention entries at head dim 256 (sliding window, attention sinks, any group size G = Hq / Hkv in
 // 1 ... 16, softmax scale, logit soft-capping): cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16 /
 // cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16_describe (include/cln_amd_ext.h; kernel:
-// flash_attn_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16.cuh). The argument list, the checking order and the status
-// codes are those of flash_attn_prefill_paged_varlen_window_sink_softcap_anyg_bf16.hip, with paged::prefill_varlen_shape_anyg_d256 for the shape:
-// D = 256 only. softcap == 0 launches the CAP = false instantiation.
+// flash_attn_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16.cuh): the bf16 softcap entry at D = 256 and no other head
+// dim; softcap == 0 launches the CAP = false instantiation. The checks and their order are paged::window_prefill (paged_entry.h); the text is this
+// unit's own, behind paged::softcap_describe: its LDS and register clauses have no counterpart in the siblings' text.
 #include "flash_attn_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16.cuh"
 #include "paged_entry.h"
 
@@ -14,25 +14,14 @@ CLN_API int cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16(cons
                                                                             const float* sinks, void* o, float* lse, int B, int total_q, int Hq,
                                                                             int Hkv, int P, int max_pages, int page, int D, int window,
                                                                             float softmax_scale, float softcap, void* stream) {
-  paged::SoftCap sc;
-  int rc = paged::softcap_arg(softmax_scale, softcap, D, &sc);
-  if (rc != CLN_OK) return rc;
-  // 16-byte aligned up to the table, 4-byte from there on; sinks counts only when given
   const void* const in[] = {q, k_pages, v_pages, block_table, seqlens, cu_q, sinks};
-  rc = paged::prefill_args(in, sinks ? 7 : 6, o, lse, P);
-  if (rc != CLN_OK) return rc;
-  fa2d::PagedGeometry g;
-  long long slots = 0;
-  rc = paged::prefill_varlen_shape_anyg_d256(B, total_q, Hq, Hkv, max_pages, page, D, &g, &slots);
-  if (rc == CLN_OK) rc = paged::window_arg(window);
-  if (rc != CLN_OK) return rc;
-  const fa2b::PagedKV kv = {(const bf16_t*)k_pages, (const bf16_t*)v_pages, block_table, Hkv, max_pages, g.page_shift};
   const hipStream_t s = (hipStream_t)stream;
-  if (sc.cap)
-    return fa2b::launch_prefill_paged_varlen_window_sink_softcap_anyg_d256<true>(q, kv, seqlens, cu_q, sinks, o, lse, B, total_q, g.group, slots,
-                                                                                 window, sc.mult, sc.pre, sc.cap2, s);
-  return fa2b::launch_prefill_paged_varlen_window_sink_softcap_anyg_d256<false>(q, kv, seqlens, cu_q, sinks, o, lse, B, total_q, g.group, slots,
-                                                                                window, sc.mult, 0.0f, 0.0f, s);
+  return paged::window_prefill<fa2b::PagedKV, paged::kAnyGD256>(
+      in, sinks ? 7 : 6, o, lse, P, {B, total_q, Hq, Hkv, max_pages, page, D, window, softmax_scale, softcap},
+      [&](auto, auto cap, const fa2b::PagedKV& kv, const paged::WindowLaunch& w) {
+        return fa2b::launch_prefill_paged_varlen_window_sink_softcap_anyg_d256<cap()>(q, kv, seqlens, cu_q, sinks, o, lse, B, total_q, w.g.group,
+                                                                                      w.slots, window, w.sc.mult, w.sc.pre, w.sc.cap2, s);
+      });
 }
 
 CLN_API int cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16_describe(int B, int total_q, int Hq, int Hkv, int max_pages, int page,
@@ -44,8 +33,7 @@ CLN_API int cln_fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16_desc
   if (rc != CLN_OK) return rc;
   fa2d::PagedGeometry g;
   long long slots = 0;
-  rc = paged::prefill_varlen_shape_anyg_d256(B, total_q, Hq, Hkv, max_pages, page, D, &g, &slots);
-  if (rc == CLN_OK) rc = paged::window_arg(window);
+  rc = paged::window_prefill_shape<paged::kAnyGD256>({B, total_q, Hq, Hkv, max_pages, page, D, window}, &g, &slots);
   if (rc != CLN_OK) return rc;
   int n = paged::softcap_describe(buf, len, "fa2_prefill_paged_varlen_window_sink_softcap_anyg_d256_bf16_mfma", D, softmax_scale, softcap, sc, false);
   const long long span = (long long)window + paged::prefill_tile_tokens_anyg(g.group) + 2 * fa2b::kKeyStep;

@@ -1,12 +1,14 @@
 // The host side of the paged KV-cache entries (cln_kv_append_paged*, cln_fa2_prefill_paged*, cln_fa2_decode_paged*; DESIGN 4.4.6, 4.4.8 - 4.4.10,
 // 4.4.16): one definition of every argument check, shape check, plan and compile-time dispatch that the 24 compile units share. Host code only -- the kernels
 // are siblings, one body per element type, for the measured reason given there; nothing here can change a kernel's schedule. A unit keeps its
-// entry points, its PagedKV / Args struct and its describe text.
+// entry points, its PagedKV / Args struct and its describe text; the sixteen windowed bf16-query units share the entry body and the text too.
 #pragma once
 #include "flash_attn_decode_common.cuh"
 #include "flash_attn_decode_paged_multi.cuh"  // fa2pm::kKeyStep, kMaxT
 #include "flash_attn_prefill_paged.cuh"       // fa2pp::kRowTile
 #include "kv_append_paged.cuh"                // kva::grid_y
+#include <cstdarg>
+#include <cstdio>
 #include <type_traits>
 
 namespace paged {
@@ -427,6 +429,212 @@ inline int decode_args(const void* const* in, int n_in, const void* const (&out)
   if (P <= 0) return CLN_ERR_BAD_ARG;
   if (plan_rc != CLN_OK) return plan_rc;
   return fa2d::workspace_fits(p, out[2], workspace_bytes) ? CLN_OK : CLN_ERR_BAD_ARG;
+}
+
+// ---------------------------------------------------------------- the windowed bf16-query entries
+// One entry body, one plan body and one describe text per family for the sixteen units flash_attn_prefill_paged_varlen_window*.hip and
+// flash_attn_decode_paged_multi_window*.hip. A unit says what it is -- its pools KV (fa2b::PagedKV, or fa2d::PagedKV8 with the two scales), its
+// group sizes GR, its inputs in the order in which they are checked -- and launches its own kernel; the protocol is here.
+enum Groups { kPow2G, kAnyG, kAnyGD256 };                 // G in {1, 2, 4, 8}; any G in 1 ... 16; any G at D = 256 and no other head dim
+enum Sinks { kNoSinks, kSinksRequired, kSinksOptional };  // for a describe text: a launching entry counts sinks into its inputs or leaves it out
+// the numbers of an entry; T = the tokens of a sequence, or total_q of a packed prefill; the two floats are 0 where the entry has none
+struct WindowArgs {
+  int B, T, Hq, Hkv, max_pages, page, D, window;
+  float softmax_scale = 0.0f, softcap = 0.0f;
+};
+// what the checks work out for a launcher: slots for a prefill, p for a decode
+struct WindowLaunch {
+  fa2d::PagedGeometry g;
+  long long slots;
+  fa2d::Plan p;
+  SoftCap sc;
+};
+template <Groups GR>
+int window_prefill_shape(const WindowArgs& a, fa2d::PagedGeometry* g, long long* slots) {
+  constexpr auto shape = GR == kPow2G ? prefill_varlen_shape : GR == kAnyG ? prefill_varlen_shape_anyg : prefill_varlen_shape_anyg_d256;
+  const int rc = shape(a.B, a.T, a.Hq, a.Hkv, a.max_pages, a.page, a.D, g, slots);
+  return rc != CLN_OK ? rc : window_arg(a.window);
+}
+template <Groups GR>
+int window_plan(const WindowArgs& a, fa2d::PagedGeometry* g, fa2d::Plan* p) {
+  constexpr auto plan = GR == kPow2G ? multi_window_plan : GR == kAnyG ? multi_window_plan_anyg : multi_window_plan_anyg_d256;
+  return plan(a.B, a.T, a.Hq, a.Hkv, a.max_pages, a.page, a.D, a.window, g, p);
+}
+// a *_plan entry: a refusal leaves the three out-parameters alone
+template <Groups GR>
+int window_plan_entry(const WindowArgs& a, int* splits, int* chunk, long long* workspace_bytes) {
+  fa2d::PagedGeometry g;
+  fa2d::Plan p;
+  return fa2d::plan_out(window_plan<GR>(a, &g, &p), p, splits, chunk, workspace_bytes);
+}
+
+// FP8 pools are the ones with scales. Every entry's inputs begin q, k_pages, v_pages, block_table; the two scales stand at in[scales].
+template <class KV, class = void>
+constexpr bool kFp8Pools = false;
+template <class KV>
+constexpr bool kFp8Pools<KV, std::void_t<decltype(KV::k_scale)>> = true;
+template <class KV>
+KV pool_view(const void* const* in, int scales, int Hkv, int max_pages, int page_shift) {
+  using E = decltype(KV::k);
+  if constexpr (kFp8Pools<KV>)
+    return {(E)in[1], (E)in[2], (const float*)in[scales], (const float*)in[scales + 1], (const int*)in[3], Hkv, max_pages, page_shift};
+  else
+    return {(E)in[1], (E)in[2], (const int*)in[3], Hkv, max_pages, page_shift};
+}
+template <Groups GR, class F>
+int for_head_dim_of(int D, F&& f) {
+  if constexpr (GR == kAnyGD256) return for_head_dim_256(D, f);
+  else return for_head_dim(D, f);
+}
+template <Groups GR, class F>
+int for_row_tiles_of(int tiles, F&& f) {
+  static_assert(kMaxRowsAnyG == 4 * 16 && kMaxRowsD256 == 2 * 16, "for_row_tiles has 1 ... 4 row tiles of 16, for_row_tiles_d256 1 or 2");
+  if constexpr (GR == kAnyGD256) return for_row_tiles_d256(tiles, f);
+  else return for_row_tiles(tiles, f);
+}
+// f(std::true_type()) with a cap, else f(std::false_type()): an entry without the two floats has no cap, and its launcher ignores the argument
+template <class F>
+int for_cap(bool cap, F&& f) { return cap ? f(std::true_type()) : f(std::false_type()); }
+// the two floats of the entry into w->sc; a launcher passes sc.mult, sc.pre, sc.cap2, and without a cap the last two are +0 (softcap may be -0)
+inline int window_softcap(const WindowArgs& a, WindowLaunch* w) {
+  const int rc = softcap_arg(a.softmax_scale, a.softcap, a.D, &w->sc);
+  if (!w->sc.cap) w->sc.pre = w->sc.cap2 = 0.0f;
+  return rc;
+}
+
+// A packed prefill entry, in the order of its status codes: the two floats (paged::softcap_arg, before any pointer is looked at), the pointers
+// and P (paged::prefill_args on the n_in inputs q, k_pages, v_pages, block_table, seqlens, cu_q[, k_scale, v_scale][, sinks]; sinks is counted
+// where it is required or given), the shape, the window. Then launch(d, cap, kv, w) for the head dim and CAP as integral constants.
+template <class KV, Groups GR, class F>
+int window_prefill(const void* const* in, int n_in, void* o, float* lse, int P, const WindowArgs& a, F&& launch) {
+  WindowLaunch w = {};
+  int rc = window_softcap(a, &w);
+  if (rc == CLN_OK) rc = prefill_args(in, n_in, o, lse, P);
+  if (rc == CLN_OK) rc = window_prefill_shape<GR>(a, &w.g, &w.slots);
+  if (rc != CLN_OK) return rc;
+  const KV kv = pool_view<KV>(in, 6, a.Hkv, a.max_pages, w.g.page_shift);
+  return for_head_dim_of<GR>(a.D, [&](auto d) { return for_cap(w.sc.cap, [&](auto cap) { return launch(d, cap, kv, w); }); });
+}
+// A multi-token decode entry likewise: the two floats, then paged::decode_args on q, k_pages, v_pages, block_table, seqlens[, k_scale,
+// v_scale][, sinks] with the plan of its group sizes. Then launch(d, mt, cap, kv, w), mt = the row tiles of 16.
+template <class KV, Groups GR, class F>
+int window_decode(const void* const* in, int n_in, void* o, float* lse, void* workspace, long long workspace_bytes, int P, const WindowArgs& a,
+                  F&& launch) {
+  WindowLaunch w = {};
+  int rc = window_softcap(a, &w);
+  if (rc == CLN_OK) rc = decode_args(in, n_in, {o, lse, workspace}, workspace_bytes, P, window_plan<GR>(a, &w.g, &w.p), w.p);
+  if (rc != CLN_OK) return rc;
+  const KV kv = pool_view<KV>(in, 5, a.Hkv, a.max_pages, w.g.page_shift);
+  return for_head_dim_of<GR>(a.D, [&](auto d) {
+    return for_row_tiles_of<GR>(multi_tiles(a.T, w.g), [&](auto mt) {
+      return for_cap(w.sc.cap, [&](auto cap) { return launch(d, mt, cap, kv, w); });
+    });
+  });
+}
+
+// A describe text in pieces: each is written behind the last while the text fits, so a short buffer gets the head of the whole text.
+struct Text {
+  char* buf;
+  int len, n;
+  __attribute__((format(printf, 2, 3))) void add(const char* fmt, ...) {
+    if (n >= len) return;
+    va_list ap;
+    va_start(ap, fmt);
+    n += vsnprintf(buf + n, len - n, fmt, ap);
+    va_end(ap);
+  }
+  int end() const { return n < len ? n : len - 1; }  // the characters written
+};
+// The text of a packed prefill entry; the clauses that vary are the kernel's name, the group sizes, the pools and the sink. The D = 256 unit
+// words its own text.
+template <class KV, Groups GR>
+int window_prefill_describe(const char* kernel, Sinks sinks, const WindowArgs& a, char* buf, int len) {
+  if (!buf || len <= 0) return CLN_ERR_BAD_ARG;
+  fa2d::PagedGeometry g;
+  long long slots = 0;
+  const int rc = window_prefill_shape<GR>(a, &g, &slots);
+  if (rc != CLN_OK) return rc;
+  constexpr bool fp8 = kFp8Pools<KV>, anyg = GR != kPow2G;
+  constexpr int kRows = fa2pp::kRowTile, kKeys = fa2pp::kKeyStep;
+  // the keys a tile walks at most: the window of its first token, the tokens of its rows (128 / G where G divides the tile; else a tile may
+  // start inside a token), and the two steps its ends are aligned to
+  const long long span = (long long)a.window + prefill_tile_tokens_anyg(g.group) + 2 * kKeys;
+  Text t = {buf, len, 0};
+  t.add(anyg ? "%s<D=%d> G=%d" : "%s<D=%d,G=%d>", kernel, a.D, g.group);
+  t.add(" B=%d total_q=%d page=%d rows=%d keys=%d W=%d: one launch, no workspace; %lld workgroups of 256 threads (%d KV heads x %lld slots = "
+        "total_q G / %d + B, at most B of them empty), sequence b owns the slots from cu_q[b] G / %d + b, found by binary search over the "
+        "device-side offsets; a slot is a tile of %d of the T_b G query rows t G + g of its sequence, ",
+        a.B, a.T, a.page, kRows, kKeys, a.window, (long long)a.Hkv * slots, a.Hkv, slots, kRows, kRows, kRows);
+  if (anyg) t.add("(t, g) = (r / G, r mod G) by division outside the key loop, any G in 1 ... %d, ", kMaxGroupAnyG);
+  t.add("32 rows per wave, and walks the keys from the step that holds the lower edge p - W + 1 of its first token to the causal edge of its "
+        "last in steps of %d, a span of at most %lld keys whatever the length; %s no table entry and no row below that first step; S^T = K Q^T "
+        "and O^T = V^T P^T on v_mfma_f32_16x16x32_bf16, V through ds_read_b64_tr_b16, fp32 scores%s, window and causal mask by select on the "
+        "steps that cross an edge, online softmax, %sno split over the keys (S=1, C=the span)",
+        kKeys, span < g.Nmax ? span : g.Nmax,
+        fp8 ? "e4m3 K and V rows through the block table, 8 bytes per thread and row, converted to bf16 once on their way to LDS "
+              "(v_cvt_scalef32_pk_bf16_fp8, exact), once per workgroup,"
+            : "K and V rows through the block table to LDS once per workgroup,",
+        fp8 ? " times k_scale" : "", fp8 ? "the normalisation times v_scale, " : "");
+  if (sinks != kNoSinks)
+    t.add("; the sink of a row's head (fp32, natural log, unscaled%s) is folded into the fp32 (m, l) of the finished row in the epilogue, once, "
+          "and a row that sees no key stays O = 0, LSE = -inf",
+          sinks == kSinksOptional ? "; none when sinks is NULL" : "");
+  t.add("; deterministic");
+  return t.end();
+}
+// The text of a multi-token decode entry, with the same clauses.
+template <class KV, Groups GR>
+int window_decode_describe(const char* kernel, Sinks sinks, const WindowArgs& a, char* buf, int len) {
+  if (!buf || len <= 0) return CLN_ERR_BAD_ARG;
+  fa2d::PagedGeometry g;
+  fa2d::Plan p;
+  const int rc = window_plan<GR>(a, &g, &p);
+  if (rc != CLN_OK) return rc;
+  constexpr bool fp8 = kFp8Pools<KV>, anyg = GR != kPow2G;
+  const int tiles = multi_tiles(a.T, g);
+  const char* const none = sinks == kSinksOptional ? "; none when sinks is NULL" : "";
+  Text t = {buf, len, 0};
+  t.add("%s<D=%d,MT=%d> T=%d G=%d W=%d span=%lld S=%d C=%d page=%d: the S splits of C keys divide the span from base = align_down(max(0, len - T "
+        "- W + 1), %lld) on, no table entry and no row below base; 4 waves split the %d-key steps, %s, each row loaded once for the %d query rows "
+        "(T x G, %d tiles of 16",
+        kernel, a.D, tiles, a.T, g.group, a.window, multi_window_span(a.T, a.page, a.window, g.Nmax), p.splits, p.chunk, a.page,
+        multi_window_unit(a.page), fa2pm::kKeyStep,
+        fp8 ? "e4m3 K and V rows through the block table to registers, 16 bytes per lane, converted to bf16 once (v_cvt_scalef32_pk_bf16_fp8, "
+              "exact): K to MFMA fragments, V through a transposed LDS read"
+            : "K rows through the block table straight to MFMA fragments, V rows through a transposed LDS read",
+        a.T * g.group, tiles);
+  if (anyg) t.add("; (t, g) = (r / G, r mod G) by division outside the key loop, any G in 1 ... %d with T G <= %d", kMaxGroupAnyG, kMaxRowsAnyG);
+  t.add(") of its KV head, S^T = K Q^T and O^T = V^T P^T on v_mfma_f32_16x16x32_bf16, fp32 scores%s, window and causal mask by select, online "
+        "softmax%s",
+        fp8 ? " times k_scale" : "", fp8 ? ", the partial times v_scale" : "");
+  if (p.splits == 1 && sinks != kNoSinks)
+    t.add("; the sink of a row's head (fp32, natural log, unscaled%s) is folded into the fp32 (m, l) of the finished row at its final store, "
+          "once, and a row that sees no key stays O = 0, LSE = -inf",
+          none);
+  if (p.splits > 1) {
+    t.add("; then fa2_decode_combine_window%s_bf16_rows<D=%d> merges the live splits ceil((len - base) / C) of a query row by log-sum-exp in "
+          "ascending order (workspace %lld bytes)",
+          sinks != kNoSinks ? "_sink" : "", a.D, p.ws_bytes);
+    if (sinks != kNoSinks) {
+      t.add(" and folds the sink of the row's head (fp32, natural log, unscaled%s", none);
+      if (sinks == kSinksOptional) t.add(": fa2_decode_combine_window_bf16_rows<D=%d> then", a.D);
+      t.add(") into the merged fp32 (m, l), once: the splits store raw partials, and a row that sees no key stays O = 0, LSE = -inf");
+    }
+  }
+  t.add("; deterministic");
+  return t.end();
+}
+// A *_softcap_* describe: the buffer, the two floats, then paged::softcap_describe as the head of the text and behind it the any-G sibling's,
+// which rest(buf, len) writes; a refusal of the sibling's is this entry's.
+template <class F>
+int softcap_describe_then(char* buf, int len, const char* kernel, const WindowArgs& a, bool fp8, F&& rest) {
+  if (!buf || len <= 0) return CLN_ERR_BAD_ARG;
+  SoftCap sc;
+  int rc = softcap_arg(a.softmax_scale, a.softcap, a.D, &sc);
+  if (rc != CLN_OK) return rc;
+  const int n = softcap_describe(buf, len, kernel, a.D, a.softmax_scale, a.softcap, sc, fp8);
+  rc = rest(buf + n, len - n);
+  return rc < 0 ? rc : n + rc;
 }
 
 // ---------------------------------------------------------------- the DSA indexer (the *_index_* entries)

@@ -108,3 +108,36 @@ def test_window_plan_siblings_return_the_same_status_and_plan(lib):
                 seen_split += pow2[0][1] > 1
             seen_anyg_only += anyg[0][0] == 0 and pow2[0][0] != 0
     assert seen_ok and seen_split and seen_anyg_only  # (8, 3) is no integer group; (3, 1) and (16, 1) are groups only the any-G forms take
+
+
+@pytest.mark.parametrize("family", ("fa2_prefill_paged_varlen", "fa2_decode_paged_multi"))
+def test_window_describe_siblings_return_the_same_status(lib, family):
+    """The windowed describe entries, cln_<name>_describe(B, T | total_q, Hq, Hkv, max_pages, page, D, window[, softmax_scale, softcap], buf,
+    len): one shape check per family in csrc/paged_entry.h for the power-of-two forms and one for the any-G forms (the softcap forms at the
+    default scale and no cap), and what the former accept the latter accept."""
+    def entries(names):
+        fns = []
+        for n in names:
+            fn = getattr(lib, "cln_%s_describe" % n.replace("fa2_decode_paged_multi", family))
+            floats = (0.0, 0.0) if "softcap" in n else ()
+            fn.argtypes, fn.restype = [ctypes.c_int] * 8 + [ctypes.c_float] * len(floats) + [ctypes.c_char_p, ctypes.c_int], ctypes.c_int
+            fns.append((fn, floats))
+        return fns
+
+    pow2_fns, anyg_fns = entries(WINDOW_POW2), entries(WINDOW_ANYG)
+    buf = ctypes.create_string_buffer(4096)
+    calls = seen_ok = seen_anyg_only = 0
+    for shape in _shapes():
+        for W in WINDOWS:
+            dims = shape + (W,)
+            # a describe entry returns the length of its text, which is the sibling's own, or a negative status
+            pow2 = [min(fn(*dims, *floats, buf, 4096), 0) for fn, floats in pow2_fns]
+            anyg = [min(fn(*dims, *floats, buf, 4096), 0) for fn, floats in anyg_fns]
+            assert len(set(pow2)) == 1, (dims, dict(zip(WINDOW_POW2, pow2)))
+            assert len(set(anyg)) == 1, (dims, dict(zip(WINDOW_ANYG, anyg)))
+            if pow2[0] == 0:
+                assert anyg[0] == 0, (dims, anyg[0])
+                seen_ok += 1
+            seen_anyg_only += anyg[0] == 0 and pow2[0] != 0
+            calls += len(pow2) + len(anyg)
+    assert calls == 7 * 16128 * len(WINDOWS) and seen_ok and seen_anyg_only  # the whole sweep ran, and it is not a sweep of refusals only
