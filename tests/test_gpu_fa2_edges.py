@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import fa_reference as far
+from fa_reference import SENTINEL, guarded, pads  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -149,30 +150,6 @@ def test_long_sequences(built, causal, D, N):
 
 
 # ---- c. guard bands: every tensor is batches 1..B of a [B + 2, ...] buffer; input pads NaN, output pads a finite sentinel
-
-SENTINEL = {torch.float16: (torch.int16, 0x3A5C), torch.float32: (torch.int32, 0x3F4B5A69)}  # 0.7949 / 0.7943: finite, unlikely results
-
-
-def guarded(shape, dtype, payload=None):
-    """(buffer, its middle slice). payload given: an input (pads NaN); None: an output (pads the sentinel, the slice NaN)."""
-    B = shape[0]
-    buf = torch.empty((B + 2,) + tuple(shape[1:]), dtype=dtype, device="cuda")
-    mid = buf[1:B + 1]
-    if payload is not None:
-        buf.fill_(float("nan"))
-        mid.copy_(payload)
-    else:
-        it, bits = SENTINEL[dtype]
-        buf.view(it).fill_(bits)
-        mid.fill_(float("nan"))
-    assert mid.is_contiguous() and mid.data_ptr() % 16 == 0 and mid.data_ptr() > buf.data_ptr()
-    return buf, mid
-
-
-def pads(buf):
-    it = SENTINEL[buf.dtype][0]
-    return torch.stack((buf[0].view(it), buf[-1].view(it))).clone()
-
 
 @pytest.mark.parametrize("causal", [False, True])
 @pytest.mark.parametrize("D", [64, 128])
