@@ -608,6 +608,64 @@ def fa2_decode_paged_mla_sparse_bf16_fp8_plan(B, T, Hq, topk, max_pages, page):
     return host.fa2_decode_paged_mla_sparse_bf16_fp8_plan(B, T, Hq, topk, max_pages, page)
 
 
+def mla_index_logits_paged_varlen_bf16(q_idx, weights, idx_pool, block_table, seqlens, cu_q, logits):
+    """mla_index_logits_paged_bf16 for a packed batch: q_idx bf16 [total_q,Hi,128], weights fp32 [total_q,Hi], logits fp32
+    [total_q,ld], cu_q int32 [B+1] on the GPU; packed row r = cu_q[b] + t has vis(r) = clamp(seqlens[b], 0, cap) - (T_b - 1 - t),
+    T_b = cu_q[b+1] - cu_q[b]; a row of no sequence writes nothing. With cu_q = [0, T, 2T, …] the fixed-T entry's bits. C entry
+    cln_mla_index_logits_paged_varlen_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.mla_index_logits_paged_varlen_bf16(q_idx, weights, idx_pool, block_table, seqlens, cu_q, logits)
+
+
+def mla_index_logits_paged_varlen_bf16_fp8(q_idx, weights, idx_pool, block_table, seqlens, cu_q, logits):
+    """mla_index_logits_paged_bf16_fp8 for a packed batch: the FP8 index pool uint8 [P,page,132], everything else as in
+    mla_index_logits_paged_varlen_bf16. C entry cln_mla_index_logits_paged_varlen_bf16_fp8 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.mla_index_logits_paged_varlen_bf16_fp8(q_idx, weights, idx_pool, block_table, seqlens, cu_q, logits)
+
+
+def mla_index_topk_varlen(logits, seqlens, cu_q, topk, indices):
+    """mla_index_topk for a packed batch: logits fp32 [total_q,ld], cu_q int32 [B+1] on the GPU, indices int32 [total_q,topk], every slot of
+    every row written; n = max(clamp(seqlens[b], 0, ld) - (T_b - 1 - t), 0) for packed row r = cu_q[b] + t, a row of no sequence all -1. C
+    entry cln_mla_index_topk_varlen (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.mla_index_topk_varlen(logits, seqlens, cu_q, topk, indices)
+
+
+def fa2_decode_paged_mla_sparse_varlen_bf16(q, pool, block_table, seqlens, cu_q, indices, softmax_scale, out, lse=None, workspace=None):
+    """fa2_decode_paged_mla_sparse_bf16 for a packed batch: q bf16 [total_q,Hq,576], indices int32 [total_q,topk], out bf16 [total_q,Hq,512],
+    lse fp32 [total_q,Hq] or None, cu_q int32 [B+1] on the GPU; a slot of packed row r = cu_q[b] + t is valid iff 0 <= idx < vis(r) =
+    clamp(seqlens[b], 0, max_pages * page) - (T_b - 1 - t); a row of no sequence gets O = 0, LSE = -inf. The workspace is sized by
+    fa2_decode_paged_mla_sparse_varlen_bf16_plan. C entry cln_fa2_decode_paged_mla_sparse_varlen_bf16 (include/cln_amd_ext.h). Not a
+    reference name."""
+    from . import host
+    return host.fa2_decode_paged_mla_sparse_varlen_bf16(q, pool, block_table, seqlens, cu_q, indices, softmax_scale, out, lse, workspace)
+
+
+def fa2_decode_paged_mla_sparse_varlen_bf16_plan(total_q, Hq, topk, max_pages, page):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_sparse_varlen_bf16: fa2_decode_paged_mla_sparse_bf16_plan with total_q in the
+    place of B * T. C entry cln_fa2_decode_paged_mla_sparse_varlen_bf16_plan."""
+    from . import host
+    return host.fa2_decode_paged_mla_sparse_varlen_bf16_plan(total_q, Hq, topk, max_pages, page)
+
+
+def fa2_decode_paged_mla_sparse_varlen_bf16_fp8(q, pool, block_table, seqlens, cu_q, kv_scale, indices, softmax_scale, out, lse=None,
+                                                workspace=None):
+    """fa2_decode_paged_mla_sparse_bf16_fp8 for a packed batch: pool torch.float8_e4m3fn [P,page,576], kv_scale fp32 [1] on the GPU, everything
+    else as in fa2_decode_paged_mla_sparse_varlen_bf16. C entry cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8 (include/cln_amd_ext.h). Not a
+    reference name."""
+    from . import host
+    return host.fa2_decode_paged_mla_sparse_varlen_bf16_fp8(q, pool, block_table, seqlens, cu_q, kv_scale, indices, softmax_scale, out, lse,
+                                                            workspace)
+
+
+def fa2_decode_paged_mla_sparse_varlen_bf16_fp8_plan(total_q, Hq, topk, max_pages, page):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_sparse_varlen_bf16_fp8: exactly
+    fa2_decode_paged_mla_sparse_varlen_bf16_plan's. C entry cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_plan."""
+    from . import host
+    return host.fa2_decode_paged_mla_sparse_varlen_bf16_fp8_plan(total_q, Hq, topk, max_pages, page)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

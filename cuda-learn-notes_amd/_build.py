@@ -47,6 +47,8 @@ KERNEL_SOURCES = [
     "flash_attn_decode_paged_mla_sparse_bf16.hip", "flash_attn_decode_paged_mla_sparse_bf16_fp8.hip",
     "kv_append_paged_index_bf16.hip", "mla_index_logits_paged_bf16.hip", "mla_index_topk.hip",
     "kv_append_paged_index_bf16_fp8.hip", "mla_index_logits_paged_bf16_fp8.hip",
+    "mla_index_logits_paged_varlen_bf16.hip", "mla_index_logits_paged_varlen_bf16_fp8.hip", "mla_index_topk_varlen.hip",
+    "flash_attn_decode_paged_mla_sparse_varlen_bf16.hip", "flash_attn_decode_paged_mla_sparse_varlen_bf16_fp8.hip",
 ]
 VENDOR_SOURCES = ["hgemm_vendor.hip", "hgemm_vendor_lt.hip", "fa2_vendor_ck.hip", "yardstick_vendor.hip"]  # the last: ck_tile FMHA instances (~1 min of hipcc)
 # a comparison row whose sources are the ROCm image's ck_tile headers: if they are missing or do not compile, the vendor

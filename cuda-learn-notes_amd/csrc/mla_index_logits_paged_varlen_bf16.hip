@@ -1,0 +1,56 @@
+// Compile unit of the logits of DeepSeek-V3.2's indexer for a packed batch over the paged index-key cache in bf16:
+// cln_mla_index_logits_paged_varlen_bf16 / cln_mla_index_logits_paged_varlen_bf16_describe (include/cln_amd_ext.h; kernel:
+// mla_index_logits_paged_varlen_bf16.cuh). The checking order and the status codes are mla_index_logits_paged_bf16.hip's with
+// cu_q among the 4-byte aligned inputs, behind seqlens: the pointers (-1), then P (-1), then paged::index_logits_varlen_shape -- a
+// non-positive B, total_q, Hi, ld, max_pages or page (-1), Hi > 64, another page, max_pages page >= 2^31 or a grid that does not fit (-2).
+#include "mla_index_logits_paged_varlen_bf16.cuh"
+#include "paged_entry.h"
+
+static_assert(fa2b::idx::kDim == paged::kIdxDim && fa2b::idx::kMaxHeads == paged::kIdxMaxHeads && fa2b::idx::kChunk == paged::kIdxChunk,
+              "paged::index_logits_varlen_shape sizes the grid for this kernel's chunk");
+
+CLN_API int cln_mla_index_logits_paged_varlen_bf16(const void* q_idx, const float* weights, const void* idx_pool, const int* block_table,
+                                                   const int* seqlens, const int* cu_q, float* logits, int B, int total_q, int Hi, long long ld,
+                                                   int P, int max_pages, int page, void* stream) {
+  const void* const in[] = {q_idx, weights, idx_pool, block_table, seqlens, cu_q};
+  const int al16[] = {1, 0, 1, 0, 0, 0};
+  int rc = paged::index_args(in, al16, 6, logits, 4);
+  if (rc != CLN_OK) return rc;
+  if (P <= 0) return CLN_ERR_BAD_ARG;
+  fa2d::PagedGeometry g;
+  int cap = 0, chunks = 0;
+  long long wgs = 0;
+  rc = paged::index_logits_varlen_shape(B, total_q, Hi, ld, max_pages, page, &g, &cap, &chunks, &wgs);
+  if (rc != CLN_OK) return rc;
+  const fa2b::IndexKeys kv = {(const bf16_t*)idx_pool, block_table, P, max_pages, g.page_shift};
+  const hipStream_t s = (hipStream_t)stream;
+  return paged::pick<4, 3, 2, 1>((Hi + 15) / 16, [&](auto nhb) {
+    return fa2b::launch_mla_index_logits_varlen<nhb()>(q_idx, weights, kv, seqlens, cu_q, logits, B, total_q, Hi, cap, chunks, ld, wgs, s);
+  });
+}
+
+CLN_API int cln_mla_index_logits_paged_varlen_bf16_describe(int B, int total_q, int Hi, long long ld, int max_pages, int page, char* buf,
+                                                            int len) {
+  if (!buf || len <= 0) return CLN_ERR_BAD_ARG;
+  fa2d::PagedGeometry g;
+  int cap = 0, chunks = 0;
+  long long wgs = 0;
+  const int rc = paged::index_logits_varlen_shape(B, total_q, Hi, ld, max_pages, page, &g, &cap, &chunks, &wgs);
+  if (rc != CLN_OK) return rc;
+  const int NHB = (Hi + 15) / 16;
+  const int n = snprintf(buf, len,
+                         "mla_index_logits_paged_varlen_bf16_mfma<NHB=%d> B=%d total_q=%d Hi=%d ld=%lld cap=%d page=%d: one launch, no workspace, no "
+                         "LDS; %lld workgroups of 4 waves, one per (packed row, chunk of %d keys; %d chunks a row, sized from cap = min(max_pages "
+                         "page, ld)), a wave per %d consecutive keys in blocks of 16; packed row r is token t = r - cu_q[b] of the sequence b with "
+                         "cu_q[b] <= r < cu_q[b + 1], found by binary search over the device-side offsets (clamped to [0, total_q]); a row of no "
+                         "sequence writes nothing and reads no length, table entry or key; vis(r) = clamp(seqlens[b], 0, cap) - (T_b - 1 - t), "
+                         "T_b = cu_q[b + 1] - cu_q[b], a workgroup at or past vis returns, a key or table entry at or past vis is never read; from "
+                         "there the body of mla_index_logits_paged_bf16_mfma: per block the index keys of %d dims go from global memory straight "
+                         "into the B operand, S = Q K^T with the heads as rows on v_mfma_f32_16x16x32_bf16, %d MFMAs per block (%d blocks of 16 "
+                         "heads x 4 k-steps, %d padding heads with q = 0 and w = 0), fp32: acc = fma(w, max(s, 0), acc) over a lane's heads in "
+                         "ascending order, then the four lanes of a key by two permlane swaps, an order that depends on neither the grid, the "
+                         "batch nor the length; logits[r, j] written once for 0 <= j < vis and nothing else; deterministic",
+                         NHB, B, total_q, Hi, ld, cap, page, wgs, paged::kIdxChunk, chunks, paged::kIdxChunk / 4, paged::kIdxDim, 4 * NHB, NHB,
+                         16 * NHB - Hi);
+  return n < len ? n : len - 1;
+}

@@ -687,4 +687,28 @@ inline int index_topk_shape(int B, int T, long long ld, int topk, long long* tok
   return CLN_OK;
 }
 
+// ---------------------------------------------------------------- the packed DSA step (the *_varlen_* indexer and sparse entries)
+// The three calls behind the append for a packed batch: [total_q, ...] rows and the device-side offsets cu_q [B + 1]. A workgroup's job is a
+// packed row where the fixed-T entries have (sequence, query token), so each shape is its sibling's with total_q in the place of B T -- a
+// packed call with cu_q = [0, T, 2 T, ...] has the sibling's grid and the sibling's plan -- and B > 0 is all that is asked of B: the offsets
+// stay on the device. The status codes are the siblings'. Nothing above changes.
+inline int index_logits_varlen_shape(int B, int total_q, int Hi, long long ld, int max_pages, int page, fa2d::PagedGeometry* g, int* cap,
+                                     int* chunks, long long* wgs) {
+  if (B <= 0) return CLN_ERR_BAD_ARG;
+  return index_logits_shape(1, total_q, Hi, ld, max_pages, page, g, cap, chunks, wgs);
+}
+inline int index_topk_varlen_shape(int B, int total_q, long long ld, int topk, long long* tokens) {
+  if (B <= 0) return CLN_ERR_BAD_ARG;
+  return index_topk_shape(1, total_q, ld, topk, tokens);
+}
+// the plan has no B: a function of the packed rows only
+inline int mla_sparse_varlen_plan(int total_q, int Hq, int topk, int max_pages, int page, fa2d::PagedGeometry* g, fa2d::Plan* p) {
+  return mla_sparse_plan(1, total_q, Hq, topk, max_pages, page, g, p);
+}
+// ... and what an entry that takes B passes to decode_args and mla_describe_args as the status of its plan
+inline int mla_sparse_varlen_shape(int B, int total_q, int Hq, int topk, int max_pages, int page, fa2d::PagedGeometry* g, fa2d::Plan* p) {
+  if (B <= 0) return CLN_ERR_BAD_ARG;
+  return mla_sparse_varlen_plan(total_q, Hq, topk, max_pages, page, g, p);
+}
+
 }  // namespace paged

@@ -1947,3 +1947,167 @@ def mla_index_logits_paged_bf16_fp8(q_idx, weights, idx_pool, block_table, seqle
     rc = fn(q_idx.data_ptr(), weights.data_ptr(), idx_pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), logits.data_ptr(), B, T, Hi,
             ld, P, max_pages, page, _stream())
     _raise(name, rc, "%s: max_pages * page, B * T or B * T * ceil(cap / 1024) too large for one launch" % name)
+
+
+# ---- the packed ("varlen") DSA step: the three calls behind the append for a packed batch -- [total_q, …] rows and the
+# device-side offsets cu_q int32 [B+1] of kv_append_paged_index_bf16 / kv_append_paged_mla_bf16 -- so that one step of continuous batching
+# (a prompt chunk next to single-token decode rows) is four calls, whatever the mix. Packed row r is token t = r - cu_q[b] of the sequence b
+# with cu_q[b] <= r < cu_q[b+1]; T_b = cu_q[b+1] - cu_q[b] takes the place of T in vis; T_b = 0 is a sequence without a token this step. The
+# offsets are clamped to [0, total_q] on the device; a row of no sequence reads no pool, table or length
+_DSA_VARLEN_TOO_LARGE = "%s: max_pages * page, total_q * Hq or total_q * ceil(Hq / 64) * splits too large for one launch"
+
+
+def _index_logits_varlen(name, fp8, q_idx, weights, idx_pool, block_table, seqlens, cu_q, logits):
+    """The body of the two packed logits entries: q_idx bf16 [total_q,Hi,128], weights fp32 [total_q,Hi], logits fp32 [total_q,ld]."""
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 7 + [ctypes.c_int] * 3 + [ctypes.c_longlong] + [ctypes.c_int] * 3 + [ctypes.c_void_p])
+    _decode_check((q_idx,) if fp8 else (q_idx, idx_pool), (block_table, seqlens, cu_q), torch.bfloat16)
+    for t in (weights, logits):
+        _check_dtype(t, torch.float32)
+    if fp8:
+        P, page = _index_pool_fp8(name, idx_pool)
+    _check_dev(idx_pool, weights, logits)
+    if q_idx.dim() != 3 or idx_pool.dim() != 3 or block_table.dim() != 2 or logits.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    total_q, Hi, D = q_idx.shape
+    ld = logits.shape[1]
+    if D != _IDX_DIM:
+        raise RuntimeError("%s: q_idx of %d dims not supported (%d)" % (name, D, _IDX_DIM))
+    if not fp8:
+        P, page, _ = idx_pool.shape
+        _check_shape(idx_pool, P, page, _IDX_DIM)
+    B, max_pages = block_table.shape
+    _check_shape(weights, total_q, Hi)
+    _check_shape(seqlens, B)
+    _check_shape(cu_q, B + 1)
+    _check_shape(logits, total_q, ld)
+    if Hi > _IDX_MAX_HEADS:
+        raise RuntimeError("%s: %d index heads not supported (1 … %d)" % (name, Hi, _IDX_MAX_HEADS))
+    if page not in _PAGED_PAGES:
+        raise _paged_page_error(name, page)
+    rc = fn(q_idx.data_ptr(), weights.data_ptr(), idx_pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), cu_q.data_ptr(),
+            logits.data_ptr(), B, total_q, Hi, ld, P, max_pages, page, _stream())
+    _raise(name, rc, "%s: max_pages * page or total_q * ceil(cap / 1024) too large for one launch" % name)
+
+
+def mla_index_logits_paged_varlen_bf16(q_idx, weights, idx_pool, block_table, seqlens, cu_q, logits):
+    """mla_index_logits_paged_bf16 for a packed batch; one launch, no workspace. q_idx torch.bfloat16 [total_q,Hi,128]; weights fp32
+    [total_q,Hi]; idx_pool torch.bfloat16 [P,page,128]; block_table int32 [B,max_pages]; seqlens int32 [B] (the lengths AFTER the append);
+    cu_q int32 [B+1] on the GPU, never read by the host; logits fp32 [total_q,ld], contiguous. For packed row r = cu_q[b] + t writes
+    logits[r,j] = sum_h weights[r,h] * max(0, q_idx[r,h] . k_idx[j]) for 0 <= j < vis(r) = clamp(seqlens[b], 0, cap) - (T_b - 1 - t),
+    T_b = cu_q[b+1] - cu_q[b], cap = min(max_pages * page, ld), and nothing else; a row of no sequence (in front of cu_q[0], at or behind
+    cu_q[B]) writes nothing. T_b = 0 is legal. With cu_q = [0, T, 2T, …] the bits of mla_index_logits_paged_bf16 on the same tensors. Hi in
+    1 … 64. Deterministic. C entry cln_mla_index_logits_paged_varlen_bf16 (include/cln_amd_ext.h); no CPU path."""
+    _index_logits_varlen("mla_index_logits_paged_varlen_bf16", False, q_idx, weights, idx_pool, block_table, seqlens, cu_q, logits)
+
+
+def mla_index_logits_paged_varlen_bf16_fp8(q_idx, weights, idx_pool, block_table, seqlens, cu_q, logits):
+    """mla_index_logits_paged_bf16_fp8 for a packed batch: idx_pool torch.uint8 [P,page,132] (the layout: index_pool_fp8_views), the scale of
+    a key once after the head sum; the packed convention, vis, the rows of no sequence and everything else as in
+    mla_index_logits_paged_varlen_bf16. With cu_q = [0, T, 2T, …] the bits of mla_index_logits_paged_bf16_fp8. Deterministic. C entry
+    cln_mla_index_logits_paged_varlen_bf16_fp8 (include/cln_amd_ext.h); no CPU path."""
+    _index_logits_varlen("mla_index_logits_paged_varlen_bf16_fp8", True, q_idx, weights, idx_pool, block_table, seqlens, cu_q, logits)
+
+
+def mla_index_topk_varlen(logits, seqlens, cu_q, topk, indices):
+    """mla_index_topk for a packed batch; one launch, no workspace. logits fp32 [total_q,ld], contiguous; seqlens int32 [B]; cu_q int32 [B+1]
+    on the GPU; indices int32 [total_q,topk], contiguous, every slot of every row written on every call. For packed row r = cu_q[b] + t,
+    n = max(clamp(seqlens[b], 0, ld) - (T_b - 1 - t), 0) and the list is mla_index_topk's: dense for n <= topk, else the topk first under
+    (logit descending, position ascending) in ascending position order. A row of no sequence gets topk times -1 and reads nothing. The list is
+    what fa2_decode_paged_mla_sparse_varlen_bf16 takes. Deterministic. C entry cln_mla_index_topk_varlen (include/cln_amd_ext.h); no CPU path."""
+    name = "mla_index_topk_varlen"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 2 + [ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p])
+    _check_dtype(logits, torch.float32)
+    for t in (seqlens, cu_q, indices):
+        _check_dtype(t, torch.int32)
+    _check_dev(logits, seqlens, cu_q, indices)
+    if logits.dim() != 2 or indices.dim() != 2 or seqlens.dim() != 1:
+        raise RuntimeError("Tensor size mismatch!")
+    total_q, ld = logits.shape
+    B = seqlens.shape[0]
+    topk = int(topk)
+    _check_shape(cu_q, B + 1)
+    _check_shape(indices, total_q, topk)
+    rc = fn(logits.data_ptr(), seqlens.data_ptr(), cu_q.data_ptr(), indices.data_ptr(), B, total_q, ld, topk, _stream())
+    _raise(name, rc, "%s: ld, total_q or topk * total_q too large for one launch" % name)
+
+
+def fa2_decode_paged_mla_sparse_varlen_bf16_plan(total_q, Hq, topk, max_pages, page):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_sparse_varlen_bf16: fa2_decode_paged_mla_sparse_bf16_plan with total_q in the
+    place of B * T -- a function of the packed rows, not of the offsets (cln_fa2_decode_paged_mla_sparse_varlen_bf16_plan,
+    include/cln_amd_ext.h). Hq in 1 … 128, topk >= 1. No GPU needed."""
+    return _mla_sparse_varlen_plan("fa2_decode_paged_mla_sparse_varlen_bf16", total_q, Hq, topk, max_pages, page)
+
+
+def fa2_decode_paged_mla_sparse_varlen_bf16_fp8_plan(total_q, Hq, topk, max_pages, page):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_sparse_varlen_bf16_fp8: exactly fa2_decode_paged_mla_sparse_varlen_bf16_plan's
+    (cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_plan, include/cln_amd_ext.h). No GPU needed."""
+    return _mla_sparse_varlen_plan("fa2_decode_paged_mla_sparse_varlen_bf16_fp8", total_q, Hq, topk, max_pages, page)
+
+
+def _mla_sparse_varlen_plan(name, total_q, Hq, topk, max_pages, page):
+    dims = tuple(map(int, (total_q, Hq, topk, max_pages, page)))
+    rc, plan = _decode_plan("cln_%s_plan" % name, dims)
+    if rc == -2:
+        if dims[1] > _MLA_MAX_HQ:
+            raise RuntimeError("%s: %d query heads not supported (1 … %d)" % (name, dims[1], _MLA_MAX_HQ))
+        if dims[-1] not in _PAGED_PAGES:
+            raise _paged_page_error(name, dims[-1])
+        raise RuntimeError(_DSA_VARLEN_TOO_LARGE % name)
+    _raise(name, rc)
+    return plan
+
+
+def _mla_sparse_varlen(name, plan, q, pool, block_table, seqlens, cu_q, kv_scale, indices, softmax_scale, out, lse, workspace):
+    """The body of the two packed sparse entries: q bf16 [total_q,Hq,576], indices int32 [total_q,topk], out bf16 [total_q,Hq,512], lse fp32
+    [total_q,Hq]; the pool holds bf16, or for the *_fp8 entry e4m3 with kv_scale: one more input pointer behind cu_q."""
+    fp8 = name.endswith("_fp8")
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * (9 + fp8) + [ctypes.c_longlong] + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_void_p])
+    scale = _softmax_scale(name, softmax_scale)
+    _decode_check((q, out) if fp8 else (q, pool, out), (block_table, seqlens, cu_q, indices), torch.bfloat16)
+    if fp8:
+        _mla_fp8_check(name, pool, kv_scale)
+    if q.dim() != 3 or pool.dim() != 3 or block_table.dim() != 2 or indices.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    total_q, Hq, Dk = q.shape
+    P, page, _ = pool.shape
+    if Dk != _MLA_DK:
+        raise RuntimeError("%s: q of %d dims not supported (%d = 512 latent + 64 rotary)" % (name, Dk, _MLA_DK))
+    _check_shape(pool, P, page, _MLA_DK)
+    B, max_pages = block_table.shape
+    _check_shape(out, total_q, Hq, _MLA_DC)
+    _check_shape(seqlens, B)
+    _check_shape(cu_q, B + 1)
+    topk = indices.shape[1]
+    _check_shape(indices, total_q, topk)
+    if not indices.is_contiguous():
+        raise RuntimeError("%s: indices must be contiguous [total_q,topk]" % name)
+    lse_ptr = _decode_lse(lse, total_q, Hq)
+    ws_ptr, ws_bytes = _decode_workspace(name, plan(total_q, Hq, topk, max_pages, page)[2], workspace, q.device)
+    more = (kv_scale.data_ptr(),) if fp8 else ()
+    rc = fn(q.data_ptr(), pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), cu_q.data_ptr(), *more, indices.data_ptr(), out.data_ptr(),
+            lse_ptr, ws_ptr, ws_bytes, B, total_q, Hq, topk, P, max_pages, page, scale, _stream())
+    _raise(name, rc)
+
+
+def fa2_decode_paged_mla_sparse_varlen_bf16(q, pool, block_table, seqlens, cu_q, indices, softmax_scale, out, lse=None, workspace=None):
+    """fa2_decode_paged_mla_sparse_bf16 for a packed batch: the attention of a DeepSeek-V3.2 step that mixes prompt chunks and decode rows, one
+    call. q torch.bfloat16 [total_q,Hq,576], absorbed; pool torch.bfloat16 [P,page,576]; block_table int32 [B,max_pages]; seqlens int32 [B]
+    (the lengths AFTER the append); cu_q int32 [B+1] on the GPU, never read by the host; indices int32 [total_q,topk], contiguous (what
+    mla_index_topk_varlen writes); out torch.bfloat16 [total_q,Hq,512]; lse fp32 [total_q,Hq] or None. For packed row r = cu_q[b] + t a slot
+    is valid iff 0 <= idx < vis(r) = clamp(seqlens[b], 0, max_pages * page) - (T_b - 1 - t), T_b = cu_q[b+1] - cu_q[b]; from there every rule
+    of fa2_decode_paged_mla_sparse_bf16 holds. A row of no sequence reads no pool, table or length and gets O = 0, LSE = -inf. With
+    cu_q = [0, T, 2T, …] the plan and the bits of fa2_decode_paged_mla_sparse_bf16 on the same tensors. workspace: at least
+    fa2_decode_paged_mla_sparse_varlen_bf16_plan(...)[2] bytes; allocated here when None and the plan splits the list. Deterministic. C entry
+    cln_fa2_decode_paged_mla_sparse_varlen_bf16 (include/cln_amd_ext.h); no CPU path."""
+    _mla_sparse_varlen("fa2_decode_paged_mla_sparse_varlen_bf16", fa2_decode_paged_mla_sparse_varlen_bf16_plan, q, pool, block_table, seqlens, cu_q,
+                       None, indices, softmax_scale, out, lse, workspace)
+
+
+def fa2_decode_paged_mla_sparse_varlen_bf16_fp8(q, pool, block_table, seqlens, cu_q, kv_scale, indices, softmax_scale, out, lse=None,
+                                                workspace=None):
+    """fa2_decode_paged_mla_sparse_bf16_fp8 for a packed batch: pool torch.float8_e4m3fn [P,page,576], kv_scale fp32 [1] on the GPU as there;
+    the packed convention, vis, the rows of no sequence and everything else as in fa2_decode_paged_mla_sparse_varlen_bf16. With
+    cu_q = [0, T, 2T, …] the plan and the bits of fa2_decode_paged_mla_sparse_bf16_fp8. Deterministic. C entry
+    cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8 (include/cln_amd_ext.h); no CPU path."""
+    _mla_sparse_varlen("fa2_decode_paged_mla_sparse_varlen_bf16_fp8", fa2_decode_paged_mla_sparse_varlen_bf16_fp8_plan, q, pool, block_table, seqlens,
+                       cu_q, kv_scale, indices, softmax_scale, out, lse, workspace)

@@ -866,3 +866,45 @@ def describe_mla_index_logits_paged_bf16_fp8(B, T, Hi, ld, max_pages, page):
     import ctypes
     i, ll = ctypes.c_int, ctypes.c_longlong
     return _describe_index("cln_mla_index_logits_paged_bf16_fp8", [i, i, i, ll, i, i], tuple(int(x) for x in (B, T, Hi, ld, max_pages, page)), 4096)
+
+
+# The packed ("varlen") DSA step: [total_q, ...] rows and the device-side offsets cu_q [B + 1] in the place of [B, T, ...].
+def describe_mla_index_logits_paged_varlen_bf16(B, total_q, Hi, ld, max_pages, page):
+    """describe() for cln_mla_index_logits_paged_varlen_bf16 (include/cln_amd_ext.h): the kernel instantiation, the packed job
+    mapping, the grid and the sibling's body as text (no GPU needed). ValueError for an unsupported or invalid shape."""
+    import ctypes
+    i, ll = ctypes.c_int, ctypes.c_longlong
+    return _describe_index("cln_mla_index_logits_paged_varlen_bf16", [i, i, i, ll, i, i],
+                           tuple(int(x) for x in (B, total_q, Hi, ld, max_pages, page)), 4096)
+
+
+def describe_mla_index_logits_paged_varlen_bf16_fp8(B, total_q, Hi, ld, max_pages, page):
+    """describe() for cln_mla_index_logits_paged_varlen_bf16_fp8 (include/cln_amd_ext.h): the packed form of the FP8 logits
+    entry's text (no GPU needed). ValueError for an unsupported or invalid shape."""
+    import ctypes
+    i, ll = ctypes.c_int, ctypes.c_longlong
+    return _describe_index("cln_mla_index_logits_paged_varlen_bf16_fp8", [i, i, i, ll, i, i],
+                           tuple(int(x) for x in (B, total_q, Hi, ld, max_pages, page)), 4096)
+
+
+def describe_mla_index_topk_varlen(B, total_q, ld, topk):
+    """describe() for cln_mla_index_topk_varlen (include/cln_amd_ext.h): the kernel, the packed job mapping and the sibling's
+    select as text (no GPU needed). ValueError for an unsupported or invalid shape."""
+    import ctypes
+    i, ll = ctypes.c_int, ctypes.c_longlong
+    return _describe_index("cln_mla_index_topk_varlen", [i, i, ll, i], tuple(int(x) for x in (B, total_q, ld, topk)), 4096)
+
+
+def describe_decode_paged_mla_sparse_varlen_bf16(B, total_q, Hq, topk, max_pages, page, softmax_scale):
+    """describe() for cln_fa2_decode_paged_mla_sparse_varlen_bf16 (include/cln_amd_ext.h): the kernel, the scale in use, the
+    packed job mapping, the split of the index list and the sibling's body as text (no GPU needed). ValueError for an unsupported or invalid
+    shape or scale (the scale is required: finite and > 0)."""
+    return _describe_bf16("cln_fa2_decode_paged_mla_sparse_varlen_bf16", tuple(int(x) for x in (B, total_q, Hq, topk, max_pages, page)), 6144,
+                          (float(softmax_scale),))
+
+
+def describe_decode_paged_mla_sparse_varlen_bf16_fp8(B, total_q, Hq, topk, max_pages, page, softmax_scale):
+    """describe() for cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8 (include/cln_amd_ext.h): the packed form of the FP8 sparse
+    entry's text (no GPU needed). ValueError for an unsupported or invalid shape or scale (the scale is required: finite and > 0)."""
+    return _describe_bf16("cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8", tuple(int(x) for x in (B, total_q, Hq, topk, max_pages, page)), 6144,
+                          (float(softmax_scale),))

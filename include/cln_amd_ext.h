@@ -742,6 +742,68 @@ int cln_mla_index_logits_paged_bf16_fp8(const void* q_idx, const float* weights,
                                         void* stream);
 int cln_mla_index_logits_paged_bf16_fp8_describe(int B, int T, int Hi, long long ld, int max_pages, int page, char* buf, int len);
 
+/* ---- The packed variable-length DSA step: the three calls behind the append -- indexer logits, exact top-k,
+ * sparse MLA decode -- for the batch format the appends already take: [total_q, ...] rows and the offsets cu_q int32 [B + 1] ON THE DEVICE
+ * (the cu_seqlens_q convention of cln_fa2_prefill_paged_varlen). One step of continuous batching, a prompt chunk next to single-token decode
+ * rows, is then four calls whatever the mix, with no padding to a common T. Both caches, bf16 and FP8, are covered. Nothing above changes.
+ *
+ * One rule for all five entries. Packed row r < total_q belongs to sequence b, the largest b in [0, B) with cu_q[b] <= r; c0 = cu_q[b],
+ * T_b = cu_q[b + 1] - c0, t = r - c0, and
+ *     vis(r) = clamp(seqlens[b], 0, cap) - (T_b - 1 - t)
+ * with each entry's own cap (min(max_pages page, ld); ld; max_pages page). seqlens holds the lengths AFTER the append. From there the
+ * definition of the fixed-T entry holds word for word with row r in the place of (b, t): which logits are written, the dense list for
+ * n <= topk, a slot valid iff 0 <= idx < vis, empty slots, every split written. T_b = 0 is legal: a sequence without a token this step. The
+ * offsets are read through the clamp of cln_kv_append_paged_varlen -- every value to [0, total_q], T_b = max(., 0), the binary search over
+ * the clamped values -- so a malformed cu_q (decreasing, negative, past total_q) is outside the contract and still addresses nothing but row
+ * r < total_q. A row that belongs to no sequence (r < cu_q[0], r >= cu_q[B], or t >= T_b) reads no pool, table entry or length, and its
+ * outputs are defined: logits nothing written; top-k all topk slots -1; sparse decode O = 0 and LSE = -inf, with splits every partial
+ * written empty.
+ *
+ * Tensors: q_idx bf16 [total_q,Hi,128], weights fp32 [total_q,Hi], logits fp32 [total_q,ld], indices int32 [total_q,topk], q bf16
+ * [total_q,Hq,576], o bf16 [total_q,Hq,512], lse fp32 [total_q,Hq] or NULL; pools, block_table [B,max_pages], seqlens [B], kv_scale, ld,
+ * topk and softmax_scale as in the fixed-T entries. cu_q is 4-byte aligned and stands among the int inputs behind seqlens.
+ *
+ * With cu_q = [0, T, 2 T, ..., B T] every entry returns the bits of its fixed-T sibling on the same tensors, and the sparse _plan is the
+ * sibling's: _plan(total_q, ...) equals cln_fa2_decode_paged_mla_sparse_bf16_plan(B, T, ...) for total_q = B T, status included. Grids:
+ * total_q ceil(cap / 1024) workgroups (logits), total_q (top-k), total_q ceil(Hq / 64) S (sparse). Nothing is read on the host, nothing
+ * is allocated: every entry can be captured into a graph, and cu_q and seqlens may change on the device between replays.
+ *
+ * Status, in the siblings' order with total_q in the place of B T. Logits: a missing or misaligned pointer (q_idx, idx_pool 16 bytes; weights,
+ * block_table, seqlens, cu_q, logits 4) or logits equal to an input (-1); P <= 0 (-1); a non-positive B, total_q, Hi, ld, max_pages or page
+ * (-1); Hi > 64, another page, max_pages page >= 2^31 or a grid that does not fit (-2). Top-k: a missing or misaligned pointer (all 4 bytes)
+ * or indices equal to an input (-1); a non-positive B, total_q, ld or topk (-1); ld >= 2^31, topk total_q past 2^61 or a grid that does not
+ * fit (-2). Sparse: the scale (-1); a missing or misaligned pointer (q, pool, o, lse, workspace 16 bytes; block_table, seqlens, cu_q,
+ * [kv_scale,] indices 4) or an output equal to an input or another output (-1); P <= 0 (-1); a non-positive B, total_q, Hq or topk (-1);
+ * Hq > 128, another page, max_pages page >= 2^31 or a grid that does not fit (-2); a workspace smaller than the plan's (-1). Deterministic.
+ */
+int cln_mla_index_logits_paged_varlen_bf16(const void* q_idx, const float* weights, const void* idx_pool, const int* block_table,
+                                           const int* seqlens, const int* cu_q, float* logits, int B, int total_q, int Hi, long long ld, int P,
+                                           int max_pages, int page, void* stream);
+int cln_mla_index_logits_paged_varlen_bf16_describe(int B, int total_q, int Hi, long long ld, int max_pages, int page, char* buf, int len);
+int cln_mla_index_logits_paged_varlen_bf16_fp8(const void* q_idx, const float* weights, const void* idx_pool, const int* block_table,
+                                               const int* seqlens, const int* cu_q, float* logits, int B, int total_q, int Hi, long long ld,
+                                               int P, int max_pages, int page, void* stream);
+int cln_mla_index_logits_paged_varlen_bf16_fp8_describe(int B, int total_q, int Hi, long long ld, int max_pages, int page, char* buf, int len);
+int cln_mla_index_topk_varlen(const float* logits, const int* seqlens, const int* cu_q, int* indices, int B, int total_q, long long ld, int topk,
+                              void* stream);
+int cln_mla_index_topk_varlen_describe(int B, int total_q, long long ld, int topk, char* buf, int len);
+int cln_fa2_decode_paged_mla_sparse_varlen_bf16_plan(int total_q, int Hq, int topk, int max_pages, int page, int* splits, int* chunk,
+                                                     long long* workspace_bytes);
+int cln_fa2_decode_paged_mla_sparse_varlen_bf16(const void* q, const void* pool, const int* block_table, const int* seqlens, const int* cu_q,
+                                                const int* indices, void* o, float* lse, void* workspace, long long workspace_bytes, int B,
+                                                int total_q, int Hq, int topk, int P, int max_pages, int page, float softmax_scale,
+                                                void* stream);
+int cln_fa2_decode_paged_mla_sparse_varlen_bf16_describe(int B, int total_q, int Hq, int topk, int max_pages, int page, float softmax_scale,
+                                                         char* buf, int len);
+int cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_plan(int total_q, int Hq, int topk, int max_pages, int page, int* splits, int* chunk,
+                                                         long long* workspace_bytes);
+int cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8(const void* q, const void* pool, const int* block_table, const int* seqlens,
+                                                    const int* cu_q, const float* kv_scale, const int* indices, void* o, float* lse,
+                                                    void* workspace, long long workspace_bytes, int B, int total_q, int Hq, int topk, int P,
+                                                    int max_pages, int page, float softmax_scale, void* stream);
+int cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_describe(int B, int total_q, int Hq, int topk, int max_pages, int page,
+                                                             float softmax_scale, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
