@@ -666,6 +666,57 @@ def fa2_decode_paged_mla_sparse_varlen_bf16_fp8_plan(total_q, Hq, topk, max_page
     return host.fa2_decode_paged_mla_sparse_varlen_bf16_fp8_plan(total_q, Hq, topk, max_pages, page)
 
 
+def latent_pool_fp8_tile_views(pool):
+    """(codes, scales, k_pe) of a latent pool in DeepSeek-V3.2's own FP8 row torch.uint8 [P,page,656]: codes float8_e4m3fn
+    [P,page,512] at byte 0 of a row, scales float32 [P,page,4] at byte 512 (one per 128-dim tile, per token), k_pe bfloat16 [P,page,64] at
+    byte 528, strided views of the same storage, no copy; c[d] = bf16(fp32(code[d]) * scale[d // 128]). Not a reference name."""
+    from . import host
+    return host.latent_pool_fp8_tile_views(pool)
+
+
+def kv_append_paged_mla_bf16_fp8_tile(c_new, k_pe_new, pool, block_table, seqlens, cu_q, q=None, q_out=None, rope_table=None, rope="none",
+                                      scale_pow2=False):
+    """kv_append_paged_mla_bf16 into a latent cache in the model's own FP8 row: pool uint8 [P,page,656] in the layout of
+    latent_pool_fp8_tile_views; per live token and 128-dim tile of c scale = max(amax, 1e-4) / 448 in fp32, rounded up to a power of two with
+    scale_pow2, code = e4m3fn(clamp(c / scale, ±448)); k_pe rotated and stored as bf16, q rows as in kv_append_paged_mla_bf16; every other
+    byte keeps its value. C entry cln_kv_append_paged_mla_bf16_fp8_tile (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.kv_append_paged_mla_bf16_fp8_tile(c_new, k_pe_new, pool, block_table, seqlens, cu_q, q, q_out, rope_table, rope, scale_pow2)
+
+
+def fa2_decode_paged_mla_sparse_bf16_fp8_tile(q, pool, block_table, seqlens, indices, softmax_scale, out, lse=None, workspace=None):
+    """fa2_decode_paged_mla_sparse_bf16 over a latent cache in the model's own FP8 row: pool uint8 [P,page,656] (latent_pool_fp8_tile_views),
+    no kv_scale -- the per-token tile scales live in the rows; q bf16 [B,T,Hq,576] absorbed, indices int32 [B,T,topk] with the validity rule,
+    the empty slots and the duplicates of the bf16 entry, out bf16 [B,T,Hq,512], lse fp32 [B,T,Hq] or None, softmax_scale required, any
+    T >= 1. The bits of fa2_decode_paged_mla_sparse_bf16 on the pool dequantised to bf16. The workspace is sized by
+    fa2_decode_paged_mla_sparse_bf16_fp8_tile_plan. C entry cln_fa2_decode_paged_mla_sparse_bf16_fp8_tile (include/cln_amd_ext.h). Not a
+    reference name."""
+    from . import host
+    return host.fa2_decode_paged_mla_sparse_bf16_fp8_tile(q, pool, block_table, seqlens, indices, softmax_scale, out, lse, workspace)
+
+
+def fa2_decode_paged_mla_sparse_bf16_fp8_tile_plan(B, T, Hq, topk, max_pages, page):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_sparse_bf16_fp8_tile: exactly fa2_decode_paged_mla_sparse_bf16_plan's. C entry
+    cln_fa2_decode_paged_mla_sparse_bf16_fp8_tile_plan."""
+    from . import host
+    return host.fa2_decode_paged_mla_sparse_bf16_fp8_tile_plan(B, T, Hq, topk, max_pages, page)
+
+
+def fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile(q, pool, block_table, seqlens, cu_q, indices, softmax_scale, out, lse=None, workspace=None):
+    """fa2_decode_paged_mla_sparse_bf16_fp8_tile for a packed batch: pool uint8 [P,page,656], cu_q int32 [B+1] on the GPU, everything else as
+    in fa2_decode_paged_mla_sparse_varlen_bf16; a row of no sequence gets O = 0, LSE = -inf. C entry
+    cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile(q, pool, block_table, seqlens, cu_q, indices, softmax_scale, out, lse, workspace)
+
+
+def fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile_plan(total_q, Hq, topk, max_pages, page):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile: exactly
+    fa2_decode_paged_mla_sparse_varlen_bf16_plan's. C entry cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile_plan."""
+    from . import host
+    return host.fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile_plan(total_q, Hq, topk, max_pages, page)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

@@ -49,6 +49,8 @@ KERNEL_SOURCES = [
     "kv_append_paged_index_bf16_fp8.hip", "mla_index_logits_paged_bf16_fp8.hip",
     "mla_index_logits_paged_varlen_bf16.hip", "mla_index_logits_paged_varlen_bf16_fp8.hip", "mla_index_topk_varlen.hip",
     "flash_attn_decode_paged_mla_sparse_varlen_bf16.hip", "flash_attn_decode_paged_mla_sparse_varlen_bf16_fp8.hip",
+    "kv_append_paged_mla_bf16_fp8_tile.hip", "flash_attn_decode_paged_mla_sparse_bf16_fp8_tile.hip",
+    "flash_attn_decode_paged_mla_sparse_varlen_bf16_fp8_tile.hip",
 ]
 VENDOR_SOURCES = ["hgemm_vendor.hip", "hgemm_vendor_lt.hip", "fa2_vendor_ck.hip", "yardstick_vendor.hip"]  # the last: ck_tile FMHA instances (~1 min of hipcc)
 # a comparison row whose sources are the ROCm image's ck_tile headers: if they are missing or do not compile, the vendor
@@ -64,6 +66,15 @@ CFLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=
 EXTRA_FLAGS = {"flash_attn_m16x.hip": ["-fno-slp-vectorize"], "flash_attn_m16x_ext.hip": ["-fno-slp-vectorize"],
                "flash_attn_bwd.hip": ["-fno-slp-vectorize"], "probe/flash_attn_m16x_probe.hip": ["-fno-slp-vectorize"],
                "fa2_vendor_ck.hip": ["-I/opt/rocm/include", "-Wno-everything"]}
+# The *_fp8_tile units are built without packed fp32 ops (no v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32), for two reasons. (1) With them on,
+# fa2_decode_paged_mla_sparse_bf16_fp8_tile_mfma needs 424 registers and SPILLS 6 VGPRs; without them it compiles to 412 and 0 spills, which
+# tests/test_no_spills.py and the kernel's zero-spill condition demand. Removing the flag brings the spill back. (2) These are new units,
+# and they take no packed fp32 forms at all; the append unit gets the flag for that reason alone (it does not spill either way: 18 / 48 / 26
+# VGPRs with packed ops, 18 / 44 / 24 without). The flag is unit-wide: the decode's `acc[db] *= alpha` rescale is 128 v_mul_f32 per wave
+# and step where the siblings compile 64 v_pk_mul_f32 -- DESIGN 4.4.26 counts that among the candidate causes of its time.
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS.update({"kv_append_paged_mla_bf16_fp8_tile.hip": NO_PACKED_FP32, "flash_attn_decode_paged_mla_sparse_bf16_fp8_tile.hip": NO_PACKED_FP32,
+                    "flash_attn_decode_paged_mla_sparse_varlen_bf16_fp8_tile.hip": NO_PACKED_FP32})
 
 
 def hipcc():

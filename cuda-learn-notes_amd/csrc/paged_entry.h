@@ -711,4 +711,43 @@ inline int mla_sparse_varlen_shape(int B, int total_q, int Hq, int topk, int max
   return mla_sparse_varlen_plan(total_q, Hq, topk, max_pages, page, g, p);
 }
 
+// ---------------------------------------------------------------- the model's own FP8 latent row (the *_fp8_tile entries)
+// One pool of BYTES [P, page, 656]: 512 e4m3fn codes of c, 4 fp32 scales (one per 128-dim tile of c, per token), 64 bf16 of k_pe. The sparse
+// plans above serve as they are: the slot step is still 64 and D still 512. Nothing above changes.
+constexpr int kMlaTile = 128, kMlaTiles = kMlaDc / kMlaTile, kMlaTileRowBytes = kMlaDc + 4 * kMlaTiles + 2 * kMlaDr;
+static_assert(kMlaTileRowBytes == 656 && kMlaTileRowBytes % 16 == 0, "every row of the pool is 16-byte aligned");
+// The append: per token one wave of 64 lanes for c (8 dims a lane, a DPP row of 16 lanes a tile), then the rotary pieces of k_pe and, with q,
+// the Hq query rows as in mla_append_shape. *y = the workgroups per token. The status codes are mla_append_shape's.
+inline int mla_append_tile_shape(int B, int total_q, int Hq, int max_pages, int page, int rope_mode, bool has_q, int* page_shift, long long* y) {
+  if (B <= 0 || total_q <= 0 || Hq <= 0 || max_pages <= 0 || page <= 0) return CLN_ERR_BAD_ARG;
+  if (rope_mode < 0 || rope_mode > 2) return CLN_ERR_UNSUPPORTED;
+  fa2d::PagedGeometry g;
+  const int rc = fa2d::paged_geometry(1, 1, max_pages, page, &g);
+  if (rc != CLN_OK) return rc;
+  *page_shift = g.page_shift;
+  const long long pe = rope_mode == 1 ? kMlaDr / 16 : kMlaDr / 8;
+  *y = (kMlaDc / 8 + pe + (has_q ? Hq : 0) * (long long)mla_append_pieces(rope_mode) + kva::kThreads - 1) / kva::kThreads;
+  return *y <= 65535 ? CLN_OK : CLN_ERR_UNSUPPORTED;
+}
+// What the two sparse decode describes say behind their job mapping: the one kernel body.
+inline void mla_tile_describe_body(Text* t, const char* valid, const fa2d::Plan& p) {
+  t->add("per %d-slot step the 4 waves resolve index -> block table entry -> pool row of %d bytes [%d e4m3fn codes of c | %d fp32 scales, one "
+         "per %d-dim tile | %d bf16 of k_pe], the index fetched two steps and the table entry one step ahead of the row, four lanes per row "
+         "and 11 16-byte loads per lane (8 of codes, 1 of scales, 2 of k_pe), %s and an empty slot never addressed (zero codes, scales and "
+         "k_pe), stage c[d] = bf16_rne(fp32(e4m3(code[d])) scale[d / %d]) -- v_cvt_pk_f32_fp8 (exact), one fp32 product, v_cvt_pk_bf16_f32, one "
+         "path for every scale value -- and k_pe verbatim into one bf16 LDS image (%d bytes static, row stride %d bytes) that feeds both "
+         "products exactly as in fa2_decode_paged_mla_sparse_bf16_mfma: S^T = K Q^T from plain row reads over all %d dims (72 MFMAs per wave "
+         "and step) and O^T = V^T P^T from transposing reads of dims 0 ... %d of the same rows (64 MFMAs) on v_mfma_f32_16x16x32_bf16, fp32 "
+         "scores and accumulators, the mask by select on 64 validity flags that travel in the pad bytes of LDS rows 0 and 1, a step without "
+         "a valid slot skipped, online softmax, P rounded once to bf16, the store unscaled and O rounded once to bf16, a token without a "
+         "valid slot O = 0, LSE = -inf",
+         kMlaKeyStep, kMlaTileRowBytes, kMlaDc, kMlaTiles, kMlaTile, kMlaDr, valid, kMlaTile, kMlaKeyStep * (2 * kMlaDk + 32), 2 * kMlaDk + 32,
+         kMlaDk, kMlaDc - 1);
+  if (p.splits > 1)
+    t->add("; every split writes its raw partial (an empty one m = -inf, l = 0, O = 0), then fa2_decode_combine_bf16_all<D=%d> merges all %d "
+           "splits of a query row by log-sum-exp in ascending order (workspace %lld bytes)",
+           kMlaDc, p.splits, p.ws_bytes);
+  t->add("; deterministic");
+}
+
 }  // namespace paged

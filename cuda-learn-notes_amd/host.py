@@ -1426,6 +1426,17 @@ def _mla_fp8_check(name, pool, kv_scale):
         raise RuntimeError("Tensor size mismatch!")
 
 
+_MLA_TILE, _MLA_TILE_ROW = 128, 656  # DeepSeek-V3.2's own FP8 latent row: 512 codes + 4 fp32 scales + 64 bf16 of k_pe
+
+
+def _mla_tile_check(pool):
+    """What the *_fp8_tile entries ask of the pool: torch.uint8 of three dims on the GPU (the row of 656 bytes is checked with the shape)."""
+    _check_dtype(pool, torch.uint8)
+    _check_dev(pool)
+    if pool.dim() != 3:
+        raise RuntimeError("Tensor size mismatch!")
+
+
 def _mla_plan(name, dims, max_t, too_large):
     """The body of the MLA *_plan wrappers: the C entry cln_<name>_plan for dims = (B, T, Hq, …, max_pages, page) and its error texts. max_t
     (the T the entry takes at most, None for no cap) and too_large (what its last -2 says) are the entry's: they choose the text of a -2,
@@ -1450,20 +1461,23 @@ def _mla_decode(name, plan, q, pool, block_table, seqlens, kv_scale, indices, so
     for a *_fp8 entry e4m3 with kv_scale: one more input pointer behind seqlens; indices = the int32 [B,T,topk] of a *_sparse_* entry: one
     more input pointer there and topk behind Hq, for the entry and its plan. plan = the entry's *_plan. What an entry takes is read from its
     name, not from an argument being None: a forgotten tensor must not select another C prototype."""
-    fp8, sparse = name.endswith("_fp8"), "_sparse_" in name
+    fp8, sparse, tile = name.endswith("_fp8"), "_sparse_" in name, name.endswith("_fp8_tile")  # *_fp8_tile: bytes [P,page,656], no kv_scale
     fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * (7 + fp8 + sparse) + [ctypes.c_longlong] + [ctypes.c_int] * (6 + sparse)
                  + [ctypes.c_float, ctypes.c_void_p])
     scale = _softmax_scale(name, softmax_scale)
-    _decode_check((q, out) if fp8 else (q, pool, out), (block_table, seqlens, indices) if sparse else (block_table, seqlens), torch.bfloat16)
+    _decode_check((q, out) if fp8 or tile else (q, pool, out), (block_table, seqlens, indices) if sparse else (block_table, seqlens),
+                  torch.bfloat16)
     if fp8:
         _mla_fp8_check(name, pool, kv_scale)
+    if tile:
+        _mla_tile_check(pool)
     if q.dim() != 4 or pool.dim() != 3 or block_table.dim() != 2 or (sparse and indices.dim() != 3):
         raise RuntimeError("Tensor size mismatch!")
     B, T, Hq, Dk = q.shape
     P, page, _ = pool.shape
     if Dk != _MLA_DK:
         raise RuntimeError("%s: q of %d dims not supported (%d = 512 latent + 64 rotary)" % (name, Dk, _MLA_DK))
-    _check_shape(pool, P, page, _MLA_DK)
+    _check_shape(pool, P, page, _MLA_TILE_ROW if tile else _MLA_DK)
     if block_table.shape[0] != B:
         raise RuntimeError("Tensor size mismatch!")
     max_pages = block_table.shape[1]
@@ -1483,12 +1497,13 @@ def _mla_decode(name, plan, q, pool, block_table, seqlens, kv_scale, indices, so
     _raise(name, rc)
 
 
-def _mla_append(name, c_new, k_pe_new, pool, block_table, seqlens, cu_q, kv_scale, q, q_out, rope_table, rope):
-    """The body of the two appends to the paged latent cache. c_new: bf16 [total_q,512], k_pe_new: bf16 [total_q,64], q, q_out: bf16
-    [total_q,Hq,576]; the pool holds bf16, or for the *_fp8 entry e4m3 with kv_scale: one more input pointer behind cu_q. Unlike the GQA
-    appends, rope "none" takes q and q_out."""
-    fp8 = name.endswith("_fp8")
-    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * (9 + fp8) + [ctypes.c_int] * 8 + [ctypes.c_void_p])
+def _mla_append(name, c_new, k_pe_new, pool, block_table, seqlens, cu_q, kv_scale, q, q_out, rope_table, rope, scale_pow2=False):
+    """The body of the three appends to the paged latent cache. c_new: bf16 [total_q,512], k_pe_new: bf16 [total_q,64], q, q_out: bf16
+    [total_q,Hq,576]; the pool holds bf16, or for the *_fp8 entry e4m3 with kv_scale: one more input pointer behind cu_q, or for the
+    *_fp8_tile entry bytes [P,page,656] with scale_pow2: one more int behind the rope mode. Unlike the GQA appends, rope "none" takes q and
+    q_out."""
+    fp8, tile = name.endswith("_fp8"), name.endswith("_fp8_tile")
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * (9 + fp8) + [ctypes.c_int] * (8 + tile) + [ctypes.c_void_p])
     if rope not in _ROPE_MODES:
         raise RuntimeError("%s: rope %r not supported ('none', 'half' or 'interleaved')" % (name, rope))
     mode = _ROPE_MODES[rope]
@@ -1498,10 +1513,12 @@ def _mla_append(name, c_new, k_pe_new, pool, block_table, seqlens, cu_q, kv_scal
         raise RuntimeError("%s: rope %r needs a rope_table (kv_append_rope_table(max_pos, 64))" % (name, rope))
     if (q is None) != (q_out is None):
         raise RuntimeError("%s: q and q_out are given together or not at all" % name)
-    rows = (c_new, k_pe_new) if fp8 else (c_new, k_pe_new, pool)
+    rows = (c_new, k_pe_new) if fp8 or tile else (c_new, k_pe_new, pool)
     _decode_check(rows + (q, q_out) if q is not None else rows, (block_table, seqlens, cu_q), torch.bfloat16)
     if fp8:
         _mla_fp8_check(name, pool, kv_scale)
+    if tile:
+        _mla_tile_check(pool)
     if c_new.dim() != 2 or k_pe_new.dim() != 2 or pool.dim() != 3 or block_table.dim() != 2:
         raise RuntimeError("Tensor size mismatch!")
     total_q = c_new.shape[0]
@@ -1509,7 +1526,7 @@ def _mla_append(name, c_new, k_pe_new, pool, block_table, seqlens, cu_q, kv_scal
     B, max_pages = block_table.shape
     _check_shape(c_new, total_q, _MLA_DC)
     _check_shape(k_pe_new, total_q, _MLA_DR)
-    _check_shape(pool, P, page, _MLA_DK)
+    _check_shape(pool, P, page, _MLA_TILE_ROW if tile else _MLA_DK)
     _check_shape(seqlens, B)
     _check_shape(cu_q, B + 1)
     Hq = 1
@@ -1524,7 +1541,8 @@ def _mla_append(name, c_new, k_pe_new, pool, block_table, seqlens, cu_q, kv_scal
         raise _paged_page_error(name, page)
     rc = fn(c_new.data_ptr(), k_pe_new.data_ptr(), pool.data_ptr(), block_table.data_ptr(), seqlens.data_ptr(), cu_q.data_ptr(),
             *((kv_scale.data_ptr(),) if fp8 else ()), None if q is None else q.data_ptr(), None if q is None else q_out.data_ptr(),
-            None if rope_table is None else rope_table.data_ptr(), B, total_q, Hq, P, max_pages, page, max_pos, mode, _stream())
+            None if rope_table is None else rope_table.data_ptr(), B, total_q, Hq, P, max_pages, page, max_pos, mode,
+            *((1 if scale_pow2 else 0,) if tile else ()), _stream())
     _raise(name, rc, "%s: max_pages * page or total_q too large for one launch" % name)
 
 
@@ -2060,19 +2078,21 @@ def _mla_sparse_varlen_plan(name, total_q, Hq, topk, max_pages, page):
 def _mla_sparse_varlen(name, plan, q, pool, block_table, seqlens, cu_q, kv_scale, indices, softmax_scale, out, lse, workspace):
     """The body of the two packed sparse entries: q bf16 [total_q,Hq,576], indices int32 [total_q,topk], out bf16 [total_q,Hq,512], lse fp32
     [total_q,Hq]; the pool holds bf16, or for the *_fp8 entry e4m3 with kv_scale: one more input pointer behind cu_q."""
-    fp8 = name.endswith("_fp8")
+    fp8, tile = name.endswith("_fp8"), name.endswith("_fp8_tile")  # *_fp8_tile: bytes [P,page,656], no kv_scale
     fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * (9 + fp8) + [ctypes.c_longlong] + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_void_p])
     scale = _softmax_scale(name, softmax_scale)
-    _decode_check((q, out) if fp8 else (q, pool, out), (block_table, seqlens, cu_q, indices), torch.bfloat16)
+    _decode_check((q, out) if fp8 or tile else (q, pool, out), (block_table, seqlens, cu_q, indices), torch.bfloat16)
     if fp8:
         _mla_fp8_check(name, pool, kv_scale)
+    if tile:
+        _mla_tile_check(pool)
     if q.dim() != 3 or pool.dim() != 3 or block_table.dim() != 2 or indices.dim() != 2:
         raise RuntimeError("Tensor size mismatch!")
     total_q, Hq, Dk = q.shape
     P, page, _ = pool.shape
     if Dk != _MLA_DK:
         raise RuntimeError("%s: q of %d dims not supported (%d = 512 latent + 64 rotary)" % (name, Dk, _MLA_DK))
-    _check_shape(pool, P, page, _MLA_DK)
+    _check_shape(pool, P, page, _MLA_TILE_ROW if tile else _MLA_DK)
     B, max_pages = block_table.shape
     _check_shape(out, total_q, Hq, _MLA_DC)
     _check_shape(seqlens, B)
@@ -2111,3 +2131,71 @@ def fa2_decode_paged_mla_sparse_varlen_bf16_fp8(q, pool, block_table, seqlens, c
     cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8 (include/cln_amd_ext.h); no CPU path."""
     _mla_sparse_varlen("fa2_decode_paged_mla_sparse_varlen_bf16_fp8", fa2_decode_paged_mla_sparse_varlen_bf16_fp8_plan, q, pool, block_table, seqlens,
                        cu_q, kv_scale, indices, softmax_scale, out, lse, workspace)
+
+
+# ---- the latent cache in DeepSeek-V3.2's own FP8 row (DESIGN 4.4.26): bytes [P,page,656], a row = 512 e4m3fn codes of c, 4 fp32 scales (one
+# per 128-dim tile of c, per token), 64 bf16 of k_pe. The row FlashMLA's FP8 sparse kernels read and the serving engines write
+def latent_pool_fp8_tile_views(pool):
+    """(codes, scales, k_pe) of a latent pool in the model's own FP8 row, torch.uint8 [P,page,656] contiguous and 16-byte aligned: codes
+    torch.float8_e4m3fn [P,page,512] (byte 0 of a row), scales torch.float32 [P,page,4] (byte 512), k_pe torch.bfloat16 [P,page,64] (byte
+    528), all strided views of the pool's own storage, no copy. A stored token means c[d] = bf16(fp32(code[d]) * scale[d // 128]), one
+    rounding, and k_pe as stored. Works on any device."""
+    _check_dtype(pool, torch.uint8)
+    if pool.dim() != 3 or pool.shape[2] != _MLA_TILE_ROW or not pool.is_contiguous() or pool.data_ptr() % 16:
+        raise RuntimeError("Tensor size mismatch!")
+    if pool.shape[1] not in _PAGED_PAGES:
+        raise _paged_page_error("latent_pool_fp8_tile_views", pool.shape[1])
+    codes = pool[..., :_MLA_DC].view(torch.float8_e4m3fn)
+    scales = pool[..., _MLA_DC:_MLA_DC + 4 * (_MLA_DC // _MLA_TILE)].view(torch.float32)
+    k_pe = pool[..., _MLA_DC + 4 * (_MLA_DC // _MLA_TILE):].view(torch.bfloat16)
+    return codes, scales, k_pe
+
+
+def kv_append_paged_mla_bf16_fp8_tile(c_new, k_pe_new, pool, block_table, seqlens, cu_q, q=None, q_out=None, rope_table=None, rope="none",
+                                      scale_pow2=False):
+    """kv_append_paged_mla_bf16 into a latent cache in the model's own FP8 row; one launch. c_new torch.bfloat16 [total_q,512], k_pe_new
+    torch.bfloat16 [total_q,64]; pool torch.uint8 [P,page,656], contiguous, written in place (the layout: latent_pool_fp8_tile_views). Per
+    live token and per 128-dim tile of c, in IEEE fp32: a = max(amax |c_tile|, 1e-4), scale = a / 448, with scale_pow2 rounded up to a power
+    of two, code = e4m3fn(clamp(c * (1 / scale), ±448)), round to nearest even; the scale is stored as computed. k_pe is rotated in fp32 and
+    rounded once to bf16, q and q_out are bf16 [total_q,Hq,576] (q_out may be q): the bits kv_append_paged_mla_bf16 writes. cu_q,
+    block_table, seqlens, rope_table, the three rope modes, liveness and the untouched rows of no sequence as there; every pool byte that is
+    not a live token's 656 bytes keeps its value. Deterministic. C entry cln_kv_append_paged_mla_bf16_fp8_tile (include/cln_amd_ext.h); no
+    CPU path."""
+    _mla_append("kv_append_paged_mla_bf16_fp8_tile", c_new, k_pe_new, pool, block_table, seqlens, cu_q, None, q, q_out, rope_table, rope,
+                scale_pow2)
+
+
+def fa2_decode_paged_mla_sparse_bf16_fp8_tile_plan(B, T, Hq, topk, max_pages, page):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_sparse_bf16_fp8_tile: exactly fa2_decode_paged_mla_sparse_bf16_plan's
+    (cln_fa2_decode_paged_mla_sparse_bf16_fp8_tile_plan, include/cln_amd_ext.h). T >= 1, Hq in 1 … 128, topk >= 1. No GPU needed."""
+    return _mla_plan("fa2_decode_paged_mla_sparse_bf16_fp8_tile", (B, T, Hq, topk, max_pages, page), None, _MLA_SPARSE_TOO_LARGE)
+
+
+def fa2_decode_paged_mla_sparse_bf16_fp8_tile(q, pool, block_table, seqlens, indices, softmax_scale, out, lse=None, workspace=None):
+    """fa2_decode_paged_mla_sparse_bf16 over a latent cache in the model's own FP8 row: the attention of a DeepSeek-V3.2 step
+    on the pool kv_append_paged_mla_bf16_fp8_tile (or a serving engine) writes. q torch.bfloat16 [B,T,Hq,576], absorbed; pool torch.uint8
+    [P,page,656] (the layout: latent_pool_fp8_tile_views); there is no kv_scale, the scales live in the rows (no NaN code and finite
+    positive scales in a listed row: the caller's contract, not checked; an unlisted row is never read). indices, the validity rule, the
+    empty slots, the duplicates, block_table, seqlens, out torch.bfloat16 [B,T,Hq,512], lse, softmax_scale, any T >= 1, Hq in 1 … 128 and any
+    topk >= 1 exactly as there. The rows are dequantised on the way to LDS, c[d] = bf16(fp32(code[d]) * scale[d // 128]) with one rounding:
+    the bits of fa2_decode_paged_mla_sparse_bf16 on the pool dequantised so. workspace: at least
+    fa2_decode_paged_mla_sparse_bf16_fp8_tile_plan(...)[2] bytes; allocated here when None and the plan splits the list. Deterministic. C
+    entry cln_fa2_decode_paged_mla_sparse_bf16_fp8_tile (include/cln_amd_ext.h); no CPU path."""
+    _mla_decode("fa2_decode_paged_mla_sparse_bf16_fp8_tile", fa2_decode_paged_mla_sparse_bf16_fp8_tile_plan, q, pool, block_table, seqlens, None,
+                indices, softmax_scale, out, lse, workspace)
+
+
+def fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile_plan(total_q, Hq, topk, max_pages, page):
+    """(splits, chunk, workspace_bytes) of fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile: exactly
+    fa2_decode_paged_mla_sparse_varlen_bf16_plan's (cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile_plan, include/cln_amd_ext.h). No GPU
+    needed."""
+    return _mla_sparse_varlen_plan("fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile", total_q, Hq, topk, max_pages, page)
+
+
+def fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile(q, pool, block_table, seqlens, cu_q, indices, softmax_scale, out, lse=None, workspace=None):
+    """fa2_decode_paged_mla_sparse_bf16_fp8_tile for a packed batch: pool torch.uint8 [P,page,656] as there; the packed convention, vis, the
+    rows of no sequence (O = 0, LSE = -inf, nothing read) and everything else as in fa2_decode_paged_mla_sparse_varlen_bf16. With
+    cu_q = [0, T, 2T, …] the plan and the bits of fa2_decode_paged_mla_sparse_bf16_fp8_tile. Deterministic. C entry
+    cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile (include/cln_amd_ext.h); no CPU path."""
+    _mla_sparse_varlen("fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile", fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile_plan, q, pool,
+                       block_table, seqlens, cu_q, None, indices, softmax_scale, out, lse, workspace)

@@ -908,3 +908,30 @@ def describe_decode_paged_mla_sparse_varlen_bf16_fp8(B, total_q, Hq, topk, max_p
     entry's text (no GPU needed). ValueError for an unsupported or invalid shape or scale (the scale is required: finite and > 0)."""
     return _describe_bf16("cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8", tuple(int(x) for x in (B, total_q, Hq, topk, max_pages, page)), 6144,
                           (float(softmax_scale),))
+
+
+# The latent cache in DeepSeek-V3.2's own FP8 row of 656 bytes (DESIGN 4.4.26): 512 e4m3fn codes, 4 fp32 tile scales, 64 bf16 of k_pe.
+def describe_kv_append_paged_mla_bf16_fp8_tile(B, total_q, Hq, max_pages, page, rope_mode, scale_pow2=False):
+    """describe() for cln_kv_append_paged_mla_bf16_fp8_tile (include/cln_amd_ext.h): the kernel instantiation, the launch, the
+    row layout and the per-tile quantiser as text (no GPU needed). rope_mode: 0 / "none", 1 / "half", 2 / "interleaved". ValueError for an
+    unsupported or invalid shape."""
+    mode = {"none": 0, "half": 1, "interleaved": 2}.get(rope_mode, rope_mode)
+    if not isinstance(mode, int):
+        raise ValueError("cln_kv_append_paged_mla_bf16_fp8_tile: rope %r not supported" % (rope_mode,))
+    return _describe_bf16("cln_kv_append_paged_mla_bf16_fp8_tile", tuple(int(x) for x in (B, total_q, Hq, max_pages, page)) + (mode, int(scale_pow2)),
+                          3072)
+
+
+def describe_decode_paged_mla_sparse_bf16_fp8_tile(B, T, Hq, topk, max_pages, page, softmax_scale):
+    """describe() for cln_fa2_decode_paged_mla_sparse_bf16_fp8_tile (include/cln_amd_ext.h): the kernel, the scale in use, the
+    jobs, the row fetch, the staging with the tile scales, the LDS bytes, the MFMA counts and the combine as text (no GPU needed). ValueError
+    for an unsupported or invalid shape or scale (the scale is required: finite and > 0)."""
+    return _describe_bf16("cln_fa2_decode_paged_mla_sparse_bf16_fp8_tile", tuple(int(x) for x in (B, T, Hq, topk, max_pages, page)), 6144,
+                          (float(softmax_scale),))
+
+
+def describe_decode_paged_mla_sparse_varlen_bf16_fp8_tile(B, total_q, Hq, topk, max_pages, page, softmax_scale):
+    """describe() for cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile (include/cln_amd_ext.h): the packed form of the text
+    above (no GPU needed). ValueError for an unsupported or invalid shape or scale (the scale is required: finite and > 0)."""
+    return _describe_bf16("cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile", tuple(int(x) for x in (B, total_q, Hq, topk, max_pages, page)),
+                          6144, (float(softmax_scale),))

@@ -804,6 +804,61 @@ int cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8(const void* q, const void* p
 int cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_describe(int B, int total_q, int Hq, int topk, int max_pages, int page,
                                                              float softmax_scale, char* buf, int len);
 
+/* ---- The latent cache in DeepSeek-V3.2's OWN FP8 row: 656 bytes a token, the row FlashMLA's FP8 sparse kernels
+ * read and the serving engines write. pool is BYTES, [P, page, 656], 16-byte aligned, behind the block table and the lengths of the other
+ * latent caches. A row:
+ *     bytes   0 ... 511   512 e4m3fn codes of the latent c
+ *     bytes 512 ... 527   4 fp32 scales, one per 128-dim tile of c, for this token
+ *     bytes 528 ... 655   64 bf16 values of k_pe, rotated, NOT quantised
+ * (656 = 41 x 16: every row, its scales and its k_pe are 16-byte aligned.) A stored token means, with ONE rounding,
+ *     c[d] = bf16_rne(fp32(e4m3(code[d])) * scale[d / 128])  (one IEEE fp32 product),    k_pe[j] = the stored bf16.
+ * The layout as written here is the contract. With cln_kv_append_paged_index_bf16_fp8, cln_mla_index_logits_paged[_varlen]_bf16_fp8 and
+ * cln_mla_index_topk[_varlen] the four-call step runs on the model's two cache formats; nothing above changes.
+ *
+ * cln_kv_append_paged_mla_bf16_fp8_tile: cln_kv_append_paged_mla_bf16 with a quantising store of c. Which row goes where, liveness, the three
+ * rope modes, the q rows (bf16, q_out may be q) and the untouched rows of no sequence are that entry's, word for word; the k_pe bytes and
+ * q_out are the bits it writes. Per live token and per 128-dim tile of c, all in IEEE fp32: a = max(amax |c_tile|, 1e-4f); scale = a /
+ * 448.0f; if scale_pow2, scale = the smallest power of two >= scale (on the bits, as cln_kv_append_paged_index_bf16_fp8); inv = 1.0f /
+ * scale; code = e4m3fn, round to nearest even, of clamp(c inv, -448, 448); the scale is stored as computed (always > 0). Every pool byte
+ * that is not a live token's 656 bytes keeps its value. Inputs are finite: the caller's contract. Status, in this order: the pointers and
+ * what goes with them as in cln_kv_append_paged_mla_bf16 (-1); scale_pow2 neither 0 nor 1 (-1); then the shape as there (-1 / -2).
+ * _describe: buf / len (-1), scale_pow2 (-1), then the shape.
+ *
+ * cln_fa2_decode_paged_mla_sparse_bf16_fp8_tile: cln_fa2_decode_paged_mla_sparse_bf16's argument list with this pool; there is no kv_scale,
+ * the scales live in the rows. The validity rule 0 <= idx < vis(b, t), empty slots anywhere, a duplicate is two keys, no valid slot gives
+ * O = 0 and LSE = -inf, any T >= 1, Hq 1 ... 128, any topk, the plan and the order of the status codes are that entry's. No NaN code and
+ * finite positive scales in a LISTED row are the caller's contract, not checked; an unlisted row is never read. The rows are dequantised by
+ * the rule above on their way to LDS, so O and LSE equal cln_fa2_decode_paged_mla_sparse_bf16's on the pool dequantised to bf16 BIT FOR BIT,
+ * whatever the scales are. Status: the softmax scale (-1); a missing or misaligned pointer (q, pool, o, lse, workspace 16 bytes;
+ * block_table, seqlens, indices 4 bytes) or an output equal to an input or another output (-1); P <= 0 (-1); the plan (-1 / -2); a
+ * workspace smaller than the plan's (-1). _plan returns what cln_fa2_decode_paged_mla_sparse_bf16_plan returns, status included.
+ *
+ * cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile: the packed form, cu_q behind seqlens, as cln_fa2_decode_paged_mla_sparse_varlen_bf16:
+ * q [total_q,Hq,576], indices [total_q,topk], o [total_q,Hq,512], lse [total_q,Hq]; a row of no sequence reads nothing and gets O = 0,
+ * LSE = -inf; with cu_q = [0, T, 2 T, ...] the plan and the bits of the fixed-T entry (one kernel body, two prologues). Status and order:
+ * that entry's, without kv_scale. Deterministic, all of them.
+ */
+int cln_kv_append_paged_mla_bf16_fp8_tile(const void* c_new, const void* k_pe_new, void* pool, const int* block_table, const int* seqlens,
+                                          const int* cu_q, const void* q, void* q_out, const float* rope_table, int B, int total_q, int Hq,
+                                          int P, int max_pages, int page, int max_pos, int rope_mode, int scale_pow2, void* stream);
+int cln_kv_append_paged_mla_bf16_fp8_tile_describe(int B, int total_q, int Hq, int max_pages, int page, int rope_mode, int scale_pow2, char* buf,
+                                                   int len);
+int cln_fa2_decode_paged_mla_sparse_bf16_fp8_tile_plan(int B, int T, int Hq, int topk, int max_pages, int page, int* splits, int* chunk,
+                                                       long long* workspace_bytes);
+int cln_fa2_decode_paged_mla_sparse_bf16_fp8_tile(const void* q, const void* pool, const int* block_table, const int* seqlens,
+                                                  const int* indices, void* o, float* lse, void* workspace, long long workspace_bytes, int B,
+                                                  int T, int Hq, int topk, int P, int max_pages, int page, float softmax_scale, void* stream);
+int cln_fa2_decode_paged_mla_sparse_bf16_fp8_tile_describe(int B, int T, int Hq, int topk, int max_pages, int page, float softmax_scale,
+                                                           char* buf, int len);
+int cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile_plan(int total_q, int Hq, int topk, int max_pages, int page, int* splits, int* chunk,
+                                                              long long* workspace_bytes);
+int cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile(const void* q, const void* pool, const int* block_table, const int* seqlens,
+                                                         const int* cu_q, const int* indices, void* o, float* lse, void* workspace,
+                                                         long long workspace_bytes, int B, int total_q, int Hq, int topk, int P, int max_pages,
+                                                         int page, float softmax_scale, void* stream);
+int cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile_describe(int B, int total_q, int Hq, int topk, int max_pages, int page,
+                                                                  float softmax_scale, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
