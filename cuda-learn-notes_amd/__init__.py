@@ -717,6 +717,23 @@ def fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile_plan(total_q, Hq, topk, max
     return host.fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile_plan(total_q, Hq, topk, max_pages, page)
 
 
+def gemm_fp8_block128_bf16(a, a_scale, b, b_scale, out):
+    """Block-scaled FP8 GEMM in DeepSeek-V3's projection format on the FP8 matrix pipe: a float8_e4m3fn [M,K] with a_scale
+    fp32 [M,K/128], b float8_e4m3fn [N,K] (the nn.Linear weight as stored) with b_scale fp32 [ceil(N/128),K/128], out bfloat16 [M,N] =
+    bf16(sum_kb a_scale[m,kb] * b_scale[n//128,kb] * sum_{k in kb} a[m,k] * b[n,k]). M >= 1, N % 8 == 0, K % 128 == 0 (ValueError otherwise);
+    M <= 64 runs the skinny form, M > 64 the tile form. C entry cln_gemm_fp8_block128_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.gemm_fp8_block128_bf16(a, a_scale, b, b_scale, out)
+
+
+def quant_fp8_block128_bf16(x, codes, scales, scale_pow2=False):
+    """The activation quantiser of gemm_fp8_block128_bf16: x bfloat16 [M,K] -> codes float8_e4m3fn [M,K] and scales fp32 [M,K/128], per row and
+    128 columns scale = max(amax, 1e-4) / 448 in fp32 (rounded up to a power of two with scale_pow2), code = e4m3fn(clamp(x / scale, ±448)).
+    C entry cln_quant_fp8_block128_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.quant_fp8_block128_bf16(x, codes, scales, scale_pow2)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

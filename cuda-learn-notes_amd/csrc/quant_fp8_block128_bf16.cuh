@@ -1,0 +1,64 @@
+// The activation quantiser of the block-scaled FP8 GEMM (cln_quant_fp8_block128_bf16, include/cln_amd_ext.h): x bf16 [M, K] ->
+// codes e4m3fn [M, K] and scales fp32 [M, K/128], one scale per row and 128 columns: the A operand of cln_gemm_fp8_block128_bf16.
+//
+// Per row and 128-column block, all in IEEE fp32 -- the formula of kv_append_paged_index_bf16_fp8.cuh and
+// kv_append_paged_mla_bf16_fp8_tile.cuh, statement for statement:
+//   a     = max(max |x|, 1e-4f)
+//   scale = a / 448.0f
+//   if pow2: scale = the smallest power of two >= scale, on the bits
+//   inv   = 1.0f / scale
+//   code  = e4m3fn, round to nearest even, of clamp(x inv, -448, 448)              (kva::store_fp8, as it stands)
+// and the scale is stored as computed. Inputs are finite: the caller's contract.
+//
+// 16 threads a block: a thread loads 16 bytes (8 columns), the block's amax goes over its 16 lanes by four DPP moves inside the 16-lane row.
+// u = 16 blk + j with j = lane & 15, and the one early return tests blk only: the 16 lanes of a DPP row leave or stay together. Lane 0 of the
+// row stores the scale. Block blk = row KB + kb sits at element 128 blk of x and codes and at scales[blk]: the three tensors are contiguous.
+// Bandwidth-bound; no LDS, no atomics, one launch.
+#pragma once
+#include "kv_append_paged_fp8.cuh"  // kva::store_fp8, kva::kThreads
+#include "paged_bf16.cuh"
+
+namespace q8 {
+
+struct Args {
+  const bf16_t* x;
+  uint8_t* codes;
+  float* scales;
+  long long blocks;  // M * K / 128
+  int pow2;
+};
+
+__global__ __launch_bounds__(kva::kThreads) void quant_fp8_block128_bf16_rows(const Args a) {
+  const unsigned long long u = (unsigned long long)blockIdx.x * kva::kThreads + threadIdx.x;
+  const unsigned long long blk = u >> 4;
+  const unsigned j = (unsigned)u & 15u;
+  if (blk >= (unsigned long long)a.blocks) return;
+  const b8 x = *(const b8*)(a.x + blk * 128u + 8u * j);
+  float y[8];
+  float m = 0.0f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    y[e] = (float)x[e];
+    m = fmaxf(m, fabsf(y[e]));
+  }
+  m = fmaxf(m, cln_dpp<0xB1>(m));   // quad_perm [1,0,3,2]
+  m = fmaxf(m, cln_dpp<0x4E>(m));   // quad_perm [2,3,0,1]
+  m = fmaxf(m, cln_dpp<0x141>(m));  // row_half_mirror
+  m = fmaxf(m, cln_dpp<0x140>(m));  // row_mirror: the block's amax in its 16 lanes
+  float scale = fmaxf(m, 1e-4f) / 448.0f;
+  if (a.pow2) {
+    const unsigned bits = __float_as_uint(scale);  // positive and normal
+    if (bits & 0x007fffffu) scale = __uint_as_float((bits & 0x7f800000u) + 0x00800000u);
+  }
+  const float inv = 1.0f / scale;
+  kva::store_fp8(a.codes + blk * 128u + 8u * j, y, inv);
+  if (j == 0) a.scales[blk] = scale;
+}
+
+// workgroups of the launch, or 0 when the shape does not fit one launch
+inline long long workgroups(long long blocks) {
+  const long long wgs = (blocks * 16 + kva::kThreads - 1) / kva::kThreads;
+  return wgs <= 0x7fffffffLL ? wgs : 0;
+}
+
+}  // namespace q8

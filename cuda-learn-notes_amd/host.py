@@ -2199,3 +2199,62 @@ def fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile(q, pool, block_table, seqle
     cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile (include/cln_amd_ext.h); no CPU path."""
     _mla_sparse_varlen("fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile", fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile_plan, q, pool,
                        block_table, seqlens, cu_q, None, indices, softmax_scale, out, lse, workspace)
+
+
+# ---- the block-scaled FP8 GEMM of DeepSeek-V3's projections and the quantiser of its activations (DESIGN 4.4.27)
+_FP8_BLOCK = 128
+
+
+def gemm_fp8_block128_bf16(a, a_scale, b, b_scale, out):
+    """out = (a * a_scale) @ (b * b_scale).T with DeepSeek-V3's block scales, on the FP8 matrix pipe; one launch, no workspace. a
+    torch.float8_e4m3fn [M,K]; a_scale fp32 [M,K/128]; b torch.float8_e4m3fn [N,K] (the nn.Linear weight as stored); b_scale fp32
+    [ceil(N/128),K/128]; out torch.bfloat16 [M,N]; all contiguous, on the GPU. out[m,n] = bf16(sum_kb a_scale[m,kb] * b_scale[n//128,kb] *
+    sum_{k in kb} a[m,k] * b[n,k]): the inner sum one K = 128 MFMA, the outer sum fp32 in ascending kb, one rounding. M >= 1, N >= 8 with
+    N % 8 == 0, K >= 128 with K % 128 == 0, else ValueError. No NaN code and finite scales: the caller's contract. Deterministic. C entry
+    cln_gemm_fp8_block128_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "gemm_fp8_block128_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 + [ctypes.c_void_p])
+    for t in (a, b):
+        _check_dtype(t, torch.float8_e4m3fn)
+    for t in (a_scale, b_scale):
+        _check_dtype(t, torch.float32)
+    _check_dtype(out, torch.bfloat16)
+    if a.dim() != 2 or b.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    (M, K), N = a.shape, b.shape[0]
+    if M < 1 or N < 8 or N % 8 or K < _FP8_BLOCK or K % _FP8_BLOCK:
+        raise ValueError("%s: M=%d N=%d K=%d not supported (M >= 1, N >= 8 with N %% 8 == 0, K >= 128 with K %% 128 == 0)" % (name, M, N, K))
+    _check_dev(a, a_scale, b, b_scale, out)
+    _check_shape(b, N, K)
+    _check_shape(a_scale, M, K // _FP8_BLOCK)
+    _check_shape(b_scale, (N + _FP8_BLOCK - 1) // _FP8_BLOCK, K // _FP8_BLOCK)
+    _check_shape(out, M, N)
+    rc = fn(a.data_ptr(), a_scale.data_ptr(), b.data_ptr(), b_scale.data_ptr(), out.data_ptr(), M, N, K, _stream())
+    if rc == -2:
+        raise ValueError("%s: M=%d N=%d K=%d too large for one launch" % (name, M, N, K))
+    _raise(name, rc)
+
+
+def quant_fp8_block128_bf16(x, codes, scales, scale_pow2=False):
+    """Quantise activations for gemm_fp8_block128_bf16; one launch. x torch.bfloat16 [M,K], K % 128 == 0; codes torch.float8_e4m3fn [M,K];
+    scales fp32 [M,K/128]; all contiguous, on the GPU. Per row and 128-column block in IEEE fp32: a = max(amax |x|, 1e-4), scale = a / 448,
+    with scale_pow2 rounded up to a power of two, code = e4m3fn(clamp(x * (1 / scale), ±448)), round to nearest even; the scale is stored as
+    computed. Inputs are finite: the caller's contract. ValueError for M < 1 or another K. Deterministic. C entry cln_quant_fp8_block128_bf16
+    (include/cln_amd_ext.h); no CPU path."""
+    name = "quant_fp8_block128_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_void_p])
+    _check_dtype(x, torch.bfloat16)
+    _check_dtype(codes, torch.float8_e4m3fn)
+    _check_dtype(scales, torch.float32)
+    if x.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    M, K = x.shape
+    if M < 1 or K < _FP8_BLOCK or K % _FP8_BLOCK:
+        raise ValueError("%s: M=%d K=%d not supported (M >= 1, K >= 128 with K %% 128 == 0)" % (name, M, K))
+    _check_dev(x, codes, scales)
+    _check_shape(codes, M, K)
+    _check_shape(scales, M, K // _FP8_BLOCK)
+    rc = fn(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), M, K, 1 if scale_pow2 else 0, _stream())
+    if rc == -2:
+        raise ValueError("%s: M=%d K=%d too large for one launch" % (name, M, K))
+    _raise(name, rc)

@@ -935,3 +935,16 @@ def describe_decode_paged_mla_sparse_varlen_bf16_fp8_tile(B, total_q, Hq, topk, 
     above (no GPU needed). ValueError for an unsupported or invalid shape or scale (the scale is required: finite and > 0)."""
     return _describe_bf16("cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile", tuple(int(x) for x in (B, total_q, Hq, topk, max_pages, page)),
                           6144, (float(softmax_scale),))
+
+
+# The block-scaled FP8 GEMM of DeepSeek-V3's projections and its activation quantiser (DESIGN 4.4.27).
+def describe_gemm_fp8_block128_bf16(M, N, K):
+    """describe() for cln_gemm_fp8_block128_bf16 (include/cln_amd_ext.h): the form that runs (skinny for M <= 64, else tile), its
+    tile, grid, registers, LDS and scratch as text (no GPU needed). ValueError for an unsupported shape."""
+    return _describe_bf16("cln_gemm_fp8_block128_bf16", tuple(int(x) for x in (M, N, K)), 2048)
+
+
+def describe_quant_fp8_block128_bf16(M, K, scale_pow2=False):
+    """describe() for cln_quant_fp8_block128_bf16 (include/cln_amd_ext.h): the kernel, the launch and the per-block formula as
+    text (no GPU needed). ValueError for an unsupported shape."""
+    return _describe_bf16("cln_quant_fp8_block128_bf16", (int(M), int(K), int(scale_pow2)), 2048)

@@ -859,6 +859,32 @@ int cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile(const void* q, const vo
 int cln_fa2_decode_paged_mla_sparse_varlen_bf16_fp8_tile_describe(int B, int total_q, int Hq, int topk, int max_pages, int page,
                                                                   float softmax_scale, char* buf, int len);
 
+/* ---- Block-scaled FP8 (e4m3fn) GEMM in DeepSeek-V3's projection format, and the activation quantiser that produces its A operand
+ * (DESIGN 4.4.27). Both: one launch, no workspace, no atomics, deterministic, graph-capturable.
+ *
+ * cln_gemm_fp8_block128_bf16: a e4m3fn [M, K]; a_scale fp32 [M, K/128]; b e4m3fn [N, K] (the nn.Linear weight as stored); b_scale fp32
+ * [ceil(N/128), K/128]; out bf16 [M, N]; all contiguous.
+ *     out[m, n] = bf16_rne( sum_kb a_scale[m, kb] * b_scale[n / 128, kb] * sum_{k in block kb} fp32(a[m, k]) * fp32(b[n, k]) )
+ * The inner sum is one K = 128 FP8 matrix instruction (fp32 accumulation inside the matrix pipe); the outer sum is fp32 in ascending kb, per
+ * block s = a_scale * b_scale (one fp32 product) and acc = fmaf(s, inner, acc); one rounding to bf16 at the end. M >= 1; N >= 8 with
+ * N % 8 == 0 (the last scale block of N may be partial); K >= 128 with K % 128 == 0; M <= 64 runs the skinny form (weights straight to
+ * registers), M > 64 the tile form (128 x 128 through LDS): _describe names the form, its grid, registers and LDS. Element offsets are 64-bit
+ * (M K and N K may pass 2^32). No NaN code (0x7F, 0xFF) and finite scales: the caller's contract, not checked. Status, in this order: the
+ * shape (-2); a missing pointer, a, b or out not 16-byte aligned, a scale not 4-byte aligned, out equal to an input (-1).
+ *
+ * cln_quant_fp8_block128_bf16: x bf16 [M, K], K % 128 == 0 -> codes e4m3fn [M, K], scales fp32 [M, K/128]. Per row and 128-column block, all
+ * in IEEE fp32, the formula of cln_kv_append_paged_index_bf16_fp8: a = max(amax |x|, 1e-4f); scale = a / 448.0f; if scale_pow2, scale = the
+ * smallest power of two >= scale (on the bits); inv = 1.0f / scale; code = e4m3fn, round to nearest even, of clamp(x inv, -448, 448); the
+ * scale is stored as computed (always > 0). Inputs are finite: the caller's contract. Status, in this order: the shape (M < 1, K < 128,
+ * K % 128 != 0, or M K / 128 past one launch: -2); a missing, misaligned (x, codes 16 bytes; scales 4) or aliased pointer (-1); scale_pow2
+ * neither 0 nor 1 (-1). _describe: buf / len (-1), the shape (-2), scale_pow2 (-1).
+ */
+int cln_gemm_fp8_block128_bf16(const void* a, const float* a_scale, const void* b, const float* b_scale, void* out, int M, int N, int K,
+                               void* stream);
+int cln_gemm_fp8_block128_bf16_describe(int M, int N, int K, char* buf, int len);
+int cln_quant_fp8_block128_bf16(const void* x, void* codes, float* scales, int M, int K, int scale_pow2, void* stream);
+int cln_quant_fp8_block128_bf16_describe(int M, int K, int scale_pow2, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
