@@ -734,6 +734,16 @@ def quant_fp8_block128_bf16(x, codes, scales, scale_pow2=False):
     return host.quant_fp8_block128_bf16(x, codes, scales, scale_pow2)
 
 
+def gemm_fp8_block128_grouped_bf16(a, a_scale, b, b_scale, expert_offsets, out, form=None):
+    """Grouped (MoE) gemm_fp8_block128_bf16 in one launch: a float8_e4m3fn [M_total,K] with rows sorted by expert, a_scale fp32
+    [M_total,K/128], b float8_e4m3fn [E,N,K], b_scale fp32 [E,ceil(N/128),K/128], expert_offsets int32 [E+1] on the GPU (expert e owns rows
+    off[e] ... off[e+1]-1; empty groups allowed; nothing is read on the host), out bfloat16 [M_total,N]: an expert's rows carry the bits of
+    gemm_fp8_block128_bf16 on that expert alone; rows of no expert are not written. form None picks by M_total <= 4 E -> "skinny", else
+    "tile"; either string pins a form. C entry cln_gemm_fp8_block128_grouped_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.gemm_fp8_block128_grouped_bf16(a, a_scale, b, b_scale, expert_offsets, out, form)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

@@ -1,0 +1,71 @@
+// Compile unit of the grouped (MoE) block-scaled FP8 GEMM: cln_gemm_fp8_block128_grouped_bf16 / cln_gemm_fp8_block128_grouped_bf16_describe
+// (include/cln_amd_ext.h; kernels and plan: gemm_fp8_block128_grouped.cuh). Status: -2 for a shape outside M_total >= 1, E >= 1,
+// N >= 8 with N % 8 == 0, K >= 128 with K % 128 == 0 (or past one launch: E, or the tile form's slots, above 65535); then -1 for a missing,
+// misaligned (a, b, out 16 bytes; the scales and the offsets 4) or aliased pointer, or a form that is none of 0 (by the rule), 1 (skinny), 2 (tile).
+#include "gemm_fp8_block128_grouped.cuh"
+
+CLN_API int cln_gemm_fp8_block128_grouped_bf16(const void* a, const float* a_scale, const void* b, const float* b_scale,
+                                               const int* expert_offsets, void* out, int M_total, int E, int N, int K, int form, void* stream) {
+  g8g::Plan p;
+  const int rc = g8g::plan(M_total, E, N, K, form, &p);
+  if (rc == CLN_ERR_UNSUPPORTED) return rc;
+  if (!a || !a_scale || !b || !b_scale || !expert_offsets || !out) return CLN_ERR_BAD_ARG;
+  if (!cln_aligned16(a) || !cln_aligned16(b) || !cln_aligned16(out) || !cln_aligned(a_scale, 4) || !cln_aligned(b_scale, 4) ||
+      !cln_aligned(expert_offsets, 4))
+    return CLN_ERR_BAD_ARG;
+  if (out == a || out == b || out == (const void*)a_scale || out == (const void*)b_scale || out == (const void*)expert_offsets) return CLN_ERR_BAD_ARG;
+  if (rc != CLN_OK) return rc;  // the form
+  const g8g::Args args = {(const uint8_t*)a, (const uint8_t*)b, a_scale, b_scale, expert_offsets, (bf16_t*)out, M_total, E, N, K / g8::kBlock};
+  return g8g::launch(args, p, (hipStream_t)stream);
+}
+
+// what hipcc (ROCm 7.2) reports for the two kernels: arch VGPRs + AGPRs (the skinny kernel holds g8::skinny<1>, <2> and <4>: the largest counts)
+static void g8g_regs(const g8g::Plan& p, int* v, int* a) {
+  if (p.tile) *v = 190, *a = 64;
+  else *v = 204, *a = 16;
+}
+
+CLN_API int cln_gemm_fp8_block128_grouped_bf16_describe(int M_total, int E, int N, int K, int form, char* buf, int len) {
+  if (!buf || len <= 0) return CLN_ERR_BAD_ARG;
+  g8g::Plan p;
+  const int rc = g8g::plan(M_total, E, N, K, form, &p);
+  if (rc != CLN_OK) return rc;
+  int v = 0, ag = 0;
+  g8g_regs(p, &v, &ag);
+  char why[96];
+  if (form == g8g::kAuto)
+    snprintf(why, sizeof why, "by the rule: M_total %s %d E", p.tile ? ">" : "<=", g8g::kSkinnyMeanRows);
+  else
+    snprintf(why, sizeof why, "pinned; the rule gives %s", g8g::auto_skinny(M_total, E) ? "skinny" : "tile");
+  int n;
+  if (p.tile)
+    n = snprintf(buf, len,
+                 "gemm_fp8_block128_grouped_tile_mfma M_total=%d E=%d N=%d K=%d: form tile (%s), one launch, expert offsets read on the device "
+                 "(clamped to [0, M_total]), no workspace, no atomics, 0 bytes scratch; grid %u x %u workgroups of 256 threads (4 waves): %u N "
+                 "tiles x %u slots = floor(M_total / %d) + E, expert e owns the slots from floor(off[e] / %d) + e; a workgroup finds its expert "
+                 "by binary search over the offsets (scalar loads) and exits when its slot lies behind the expert's last tile (at most E empty "
+                 "slots; an empty expert owns none); output tile %d (m) x %d (n) from the expert's own first row, rows clamped on load to the "
+                 "expert's own last row, stores masked at the expert's end; per K block of 128 16 v_mfma_f32_16x16x128_f8f6f4 a wave (weights = "
+                 "SrcA, activations = SrcB, zero C, e4m3 both, no hardware scale), then s = sa * sb (sb from the expert's own grid) and 4 fmaf per "
+                 "sub-tile into 64 fp32 master accumulators; %d K blocks through a ring of 2 LDS slots of %d bytes, %d bytes static, filled "
+                 "through registers, 16-byte chunk c of row r at c ^ ((r >> 1) & 7); one barrier a K block; %d VGPRs + %d AGPRs, no spill; "
+                 "64-bit element offsets; deterministic: an expert's rows carry the bits of gemm_fp8_block128_bf16 on that expert alone",
+                 M_total, E, N, K, why, p.gx, p.gy, p.gx, p.gy, g8::kTileM, g8::kTileM, g8::kTileM, g8::kTileN, K / g8::kBlock, g8::kSlotBytes,
+                 g8::kTileLds, v, ag);
+  else
+    n = snprintf(buf, len,
+                 "gemm_fp8_block128_grouped_skinny_mfma M_total=%d E=%d N=%d K=%d: form skinny (%s), one launch, expert offsets read on the "
+                 "device (clamped to [0, M_total]), no workspace, no atomics, no LDS, 0 bytes scratch; grid %u x %u workgroups of %d threads "
+                 "(%d waves): %u strips of %d weight rows (a wave 16; 64-row strips where strips x E >= %d) x E experts; empty-expert exit: a "
+                 "workgroup reads off[e], off[e + 1] by scalar loads and returns before its first weight load when M_e = 0; else it walks the "
+                 "expert's rows in chunks of up to 64, MT = 1, 2 or 4 sub-tiles of 16 rows by the rows left (workgroup-uniform); weights from "
+                 "global memory straight into the MFMA operand registers (32 bytes a lane, two 16-byte loads), a ring of %d K blocks in "
+                 "registers; activations and their scales to registers one K block ahead; per K block of 128 MT "
+                 "v_mfma_f32_16x16x128_f8f6f4 a wave (weights = SrcA, activations = SrcB, zero C, e4m3 both, no hardware scale), then s = sa * sb "
+                 "(sb from the expert's own grid) and 4 fmaf per sub-tile into fp32 master accumulators; %d K blocks, no split over K; rows "
+                 "clamped on load, masked on store at the chunk's end; %d VGPRs + %d AGPRs, no spill; 64-bit element offsets; deterministic: an "
+                 "expert's rows carry the bits of gemm_fp8_block128_bf16 on that expert alone; the tile form would use %lld slots",
+                 M_total, E, N, K, why, p.gx, p.gy, 64 * p.waves, p.waves, p.gx, 16 * p.waves, g8::kCUs, g8::kPF, K / g8::kBlock, v, ag,
+                 (long long)M_total / g8::kTileM + E);
+  return n < len ? n : len - 1;
+}

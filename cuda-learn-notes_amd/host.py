@@ -2258,3 +2258,39 @@ def quant_fp8_block128_bf16(x, codes, scales, scale_pow2=False):
     if rc == -2:
         raise ValueError("%s: M=%d K=%d too large for one launch" % (name, M, K))
     _raise(name, rc)
+
+
+def gemm_fp8_block128_grouped_bf16(a, a_scale, b, b_scale, expert_offsets, out, form=None):
+    """gemm_fp8_block128_bf16 for every expert of a mixture-of-experts layer in one launch. a torch.float8_e4m3fn [M_total,K],
+    rows sorted by expert; a_scale fp32 [M_total,K/128]; b torch.float8_e4m3fn [E,N,K]; b_scale fp32 [E,ceil(N/128),K/128]; expert_offsets
+    torch.int32 [E+1] on the GPU: expert e owns the rows off[e] ... off[e+1]-1 (values are clamped to [0,M_total] on the device; empty groups
+    allowed; the host reads none of them); out torch.bfloat16 [M_total,N]; all contiguous, on the GPU. An expert's rows carry the bits of
+    gemm_fp8_block128_bf16 on that expert alone; a row of no expert is not written. form None: "skinny" for M_total <= 4 E, else "tile";
+    "skinny" / "tile" pin a form at any shape. M_total >= 1, E >= 1, N >= 8 with N % 8 == 0, K >= 128 with K % 128 == 0, else ValueError.
+    Deterministic. C entry cln_gemm_fp8_block128_grouped_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "gemm_fp8_block128_grouped_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 5 + [ctypes.c_void_p])
+    form_int = manifest.gemm_fp8_grouped_form(form)
+    for t in (a, b):
+        _check_dtype(t, torch.float8_e4m3fn)
+    for t in (a_scale, b_scale):
+        _check_dtype(t, torch.float32)
+    _check_dtype(expert_offsets, torch.int32)
+    _check_dtype(out, torch.bfloat16)
+    if a.dim() != 2 or b.dim() != 3 or expert_offsets.dim() != 1:
+        raise RuntimeError("Tensor size mismatch!")
+    (M, K), (E, N) = a.shape, b.shape[:2]
+    if M < 1 or E < 1 or N < 8 or N % 8 or K < _FP8_BLOCK or K % _FP8_BLOCK:
+        raise ValueError("%s: M_total=%d E=%d N=%d K=%d not supported (M_total >= 1, E >= 1, N >= 8 with N %% 8 == 0, K >= 128 with "
+                         "K %% 128 == 0)" % (name, M, E, N, K))
+    _check_dev(a, a_scale, b, b_scale, expert_offsets, out)
+    _check_shape(b, E, N, K)
+    _check_shape(a_scale, M, K // _FP8_BLOCK)
+    _check_shape(b_scale, E, (N + _FP8_BLOCK - 1) // _FP8_BLOCK, K // _FP8_BLOCK)
+    _check_shape(expert_offsets, E + 1)
+    _check_shape(out, M, N)
+    rc = fn(a.data_ptr(), a_scale.data_ptr(), b.data_ptr(), b_scale.data_ptr(), expert_offsets.data_ptr(), out.data_ptr(), M, E, N, K, form_int,
+            _stream())
+    if rc == -2:
+        raise ValueError("%s: M_total=%d E=%d N=%d K=%d too large for one launch" % (name, M, E, N, K))
+    _raise(name, rc)

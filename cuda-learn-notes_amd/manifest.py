@@ -948,3 +948,21 @@ def describe_quant_fp8_block128_bf16(M, K, scale_pow2=False):
     """describe() for cln_quant_fp8_block128_bf16 (include/cln_amd_ext.h): the kernel, the launch and the per-block formula as
     text (no GPU needed). ValueError for an unsupported shape."""
     return _describe_bf16("cln_quant_fp8_block128_bf16", (int(M), int(K), int(scale_pow2)), 2048)
+
+
+# The grouped (MoE) block-scaled FP8 GEMM (DESIGN 4.4.28). The `form` argument of the Python entries and the C entry's int.
+GEMM_FP8_GROUPED_FORMS = {None: 0, "skinny": 1, "tile": 2}
+
+
+def gemm_fp8_grouped_form(form):
+    """The C entry's `int form` of form None (the rule), "skinny" or "tile"; ValueError for anything else."""
+    if not (form is None or isinstance(form, str)) or form not in GEMM_FP8_GROUPED_FORMS:
+        raise ValueError("form must be None, 'skinny' or 'tile', not %r" % (form,))
+    return GEMM_FP8_GROUPED_FORMS[form]
+
+
+def describe_gemm_fp8_block128_grouped_bf16(M_total, E, N, K, form=None):
+    """describe() for cln_gemm_fp8_block128_grouped_bf16 (include/cln_amd_ext.h): the form that runs (form None: skinny for
+    M_total <= 4 E, else tile; "skinny" / "tile" pin one), its grid, the slot count floor(M_total / 128) + E, the empty-expert exit, registers,
+    LDS and scratch as text (no GPU needed). ValueError for an unsupported shape or form."""
+    return _describe_bf16("cln_gemm_fp8_block128_grouped_bf16", tuple(int(x) for x in (M_total, E, N, K, gemm_fp8_grouped_form(form))), 3072)

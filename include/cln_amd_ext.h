@@ -885,6 +885,29 @@ int cln_gemm_fp8_block128_bf16_describe(int M, int N, int K, char* buf, int len)
 int cln_quant_fp8_block128_bf16(const void* x, void* codes, float* scales, int M, int K, int scale_pow2, void* stream);
 int cln_quant_fp8_block128_bf16_describe(int M, int K, int scale_pow2, char* buf, int len);
 
+/* ---- Grouped (mixture-of-experts) block-scaled FP8 GEMM over expert offsets on the device. One
+ * launch, nothing read on the host, no workspace, no atomics, deterministic, graph-capturable with the offsets changing between replays.
+ *
+ * cln_gemm_fp8_block128_grouped_bf16: a e4m3fn [M_total, K], its rows sorted by expert (no alignment of a group's start or size); a_scale fp32
+ * [M_total, K/128] (what cln_quant_fp8_block128_bf16 writes); b e4m3fn [E, N, K] (the experts' nn.Linear weights as stored); b_scale fp32
+ * [E, ceil(N/128), K/128]; expert_offsets int32 [E + 1] in device memory: expert e owns the rows off[e] ... off[e + 1] - 1; out bf16
+ * [M_total, N]; all contiguous. For a row m of expert e
+ *     out[m, n] = bf16_rne( sum_kb a_scale[m, kb] * b_scale[e, n / 128, kb] * sum_{k in block kb} fp32(a[m, k]) * fp32(b[e, n, k]) )
+ * in the arithmetic of cln_gemm_fp8_block128_bf16: an expert's rows carry the bits that entry gives on that expert alone, in either form. The
+ * offsets are read through a clamp (every value to [0, M_total], a group's size max(., 0)): a malformed array names no row outside the
+ * tensors. A group may be empty, anywhere; a row in front of off[0] or at or behind off[E] belongs to no expert and is not written.
+ * M_total >= 1; E >= 1; N >= 8 with N % 8 == 0 (the last scale block of N may be partial); K >= 128 with K % 128 == 0. Element offsets are
+ * 64-bit (E N K may pass 2^32). form: 0 picks by the fixed rule M_total <= 4 E -> skinny, else tile; 1 pins the skinny form (grid: strips
+ * of 32 or 64 weight rows x E; an empty expert's workgroups return before their first weight load), 2 the tile form (128 x 128 tiles over
+ * floor(M_total / 128) + E slots, expert e from slot floor(off[e] / 128) + e); _describe names the form, its grid and slots, registers and
+ * LDS. No NaN code and finite scales: the caller's contract, not checked. Status, in this order: the shape, or E (skinny) or the slots (tile)
+ * above 65535 (-2); a missing pointer, a, b or out not 16-byte aligned, a scale or the offsets not 4-byte aligned, out equal to an input, a
+ * form that is none of 0, 1, 2 (-1). _describe: buf / len (-1), the shape (-2), the form (-1).
+ */
+int cln_gemm_fp8_block128_grouped_bf16(const void* a, const float* a_scale, const void* b, const float* b_scale, const int* expert_offsets,
+                                       void* out, int M_total, int E, int N, int K, int form, void* stream);
+int cln_gemm_fp8_block128_grouped_bf16_describe(int M_total, int E, int N, int K, int form, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
