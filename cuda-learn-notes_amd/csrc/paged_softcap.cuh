@@ -1,5 +1,6 @@
 // Logit soft-capping of the *_softcap_* paged attention kernels: the score of a key under a cap, s = cap tanh(q.k x / cap), in
-// the log2 units of the online softmax, and the prefill's softmax step on it. Shared by the four kernel headers; nothing else includes it.
+// the log2 units of the online softmax, and the prefill's softmax step on it. Included by the prefill body
+// (flash_attn_prefill_paged_varlen_window_body.cuh) and the *_softcap_* decode kernel headers; nothing else includes it.
 //
 // gfx950 has no tanh instruction (v_tanh_* came with later ISAs), so tanh is put together in fp32 from v_exp_f32 and v_rcp_f32. With
 // y = q.k x / cap and three wave-uniform numbers of paged::softcap_arg -- mult = x log2(e), pre = 2 log2(e) x / cap, cap2 = cap log2(e); the FP8
@@ -13,7 +14,7 @@
 // Both are computed and one is selected: no divergence. Per score that is 11 VALU instructions, two of them quarter-rate, where the uncapped
 // kernels have one multiplication.
 #pragma once
-#include "flash_attn_prefill_paged_varlen_window_bf16.cuh"  // softmax_step_window, whose sibling stands below
+#include "flash_attn_prefill_paged_varlen_bf16.cuh"  // the tile constants and the fragment types of the softmax step below
 
 namespace fa2b {
 
@@ -47,8 +48,8 @@ __device__ __forceinline__ float acc_fetch(float a) {
   return x;
 }
 
-// fa2b::softmax_step_window with the cap in front of the mask: a hidden key is -inf, not -cap. Behind the scores it is that function, statement
-// for statement.
+// fa2b::softmax_step_window (flash_attn_prefill_paged_varlen_window_body.cuh) with the cap in front of the mask: a hidden key is -inf, not
+// -cap. Behind the scores it is that function.
 template <bool MASK>
 __device__ __forceinline__ void softmax_step_window_cap(const f4 (&st)[kKB], unsigned key0, unsigned lo_q, unsigned nq, const SoftCapMul& cm, float& m,
                                                         float& l, float& alpha, b8 (&pf)[2]) {
