@@ -744,6 +744,16 @@ def gemm_fp8_block128_grouped_bf16(a, a_scale, b, b_scale, expert_offsets, out, 
     return host.gemm_fp8_block128_grouped_bf16(a, a_scale, b, b_scale, expert_offsets, out, form)
 
 
+def gemm_fp8_block128_grouped_swiglu_fp8(a, a_scale, b, b_scale, expert_offsets, h, h_scale, form=None, scale_pow2=False):
+    """The gate/up projection of an MoE expert FFN with SiLU-mul and the FP8 quantiser fused behind it, one launch: a, a_scale,
+    expert_offsets as in gemm_fp8_block128_grouped_bf16, b float8_e4m3fn [E,2I,K] (gate rows, then up rows), b_scale fp32 [E,2I/128,K/128];
+    h float8_e4m3fn [M_total,I] and h_scale fp32 [M_total,I/128] = quant_fp8_block128_bf16's rule on silu(G) * U with G, U kept in fp32: the
+    a, a_scale of the down projection. I % 128 == 0, K % 128 == 0 (ValueError otherwise); form as in gemm_fp8_block128_grouped_bf16. C entry
+    cln_gemm_fp8_block128_grouped_swiglu_fp8 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.gemm_fp8_block128_grouped_swiglu_fp8(a, a_scale, b, b_scale, expert_offsets, h, h_scale, form, scale_pow2)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

@@ -52,6 +52,7 @@ KERNEL_SOURCES = [
     "kv_append_paged_mla_bf16_fp8_tile.hip", "flash_attn_decode_paged_mla_sparse_bf16_fp8_tile.hip",
     "flash_attn_decode_paged_mla_sparse_varlen_bf16_fp8_tile.hip",
     "gemm_fp8_block128.hip", "quant_fp8_block128_bf16.hip", "gemm_fp8_block128_grouped.hip",
+    "gemm_fp8_block128_grouped_swiglu.hip",
 ]
 VENDOR_SOURCES = ["hgemm_vendor.hip", "hgemm_vendor_lt.hip", "fa2_vendor_ck.hip", "yardstick_vendor.hip"]  # the last: ck_tile FMHA instances (~1 min of hipcc)
 # a comparison row whose sources are the ROCm image's ck_tile headers: if they are missing or do not compile, the vendor
@@ -81,6 +82,8 @@ EXTRA_FLAGS.update({"kv_append_paged_mla_bf16_fp8_tile.hip": NO_PACKED_FP32, "fl
 EXTRA_FLAGS.update({"gemm_fp8_block128.hip": NO_PACKED_FP32, "quant_fp8_block128_bf16.hip": NO_PACKED_FP32})
 # Its grouped (MoE) sibling includes the dense kernel's header and is built like it.
 EXTRA_FLAGS.update({"gemm_fp8_block128_grouped.hip": NO_PACKED_FP32})
+# The fused gate/up + SiLU-mul + quantise sibling includes both headers and is built like them.
+EXTRA_FLAGS.update({"gemm_fp8_block128_grouped_swiglu.hip": NO_PACKED_FP32})
 
 
 def hipcc():

@@ -2294,3 +2294,41 @@ def gemm_fp8_block128_grouped_bf16(a, a_scale, b, b_scale, expert_offsets, out, 
     if rc == -2:
         raise ValueError("%s: M_total=%d E=%d N=%d K=%d too large for one launch" % (name, M, E, N, K))
     _raise(name, rc)
+
+
+def gemm_fp8_block128_grouped_swiglu_fp8(a, a_scale, b, b_scale, expert_offsets, h, h_scale, form=None, scale_pow2=False):
+    """The gate/up projection of an MoE expert FFN with SiLU-mul and quant_fp8_block128_bf16's rule fused behind it; one launch, no workspace
+    (DESIGN 4.4.30). a, a_scale, expert_offsets as in gemm_fp8_block128_grouped_bf16; b torch.float8_e4m3fn [E,2I,K] (an expert's rows 0 ...
+    I-1 the gate, I ... 2I-1 the up projection); b_scale fp32 [E,2I/128,K/128]; h torch.float8_e4m3fn [M_total,I]; h_scale fp32
+    [M_total,I/128]; all contiguous, on the GPU. G and U are the grouped entry's fp32 sums (never rounded to bf16), hf = G / (1 + exp(-G)) * U
+    in fp32, and per row and 128 columns scale = max(amax |hf|, 1e-4) / 448 (with scale_pow2 rounded up to a power of two), code =
+    e4m3fn(clamp(hf * (1 / scale), ±448)); a row of no expert is not written. form None: "skinny" for M_total <= 4 E, else "tile". M_total
+    >= 1, E >= 1, I >= 128 with I % 128 == 0, K >= 128 with K % 128 == 0, else ValueError. Deterministic. C entry
+    cln_gemm_fp8_block128_grouped_swiglu_fp8 (include/cln_amd_ext.h); no CPU path."""
+    name = "gemm_fp8_block128_grouped_swiglu_fp8"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 7 + [ctypes.c_int] * 6 + [ctypes.c_void_p])
+    form_int = manifest.gemm_fp8_grouped_form(form)
+    for t in (a, b, h):
+        _check_dtype(t, torch.float8_e4m3fn)
+    for t in (a_scale, b_scale, h_scale):
+        _check_dtype(t, torch.float32)
+    _check_dtype(expert_offsets, torch.int32)
+    if a.dim() != 2 or b.dim() != 3 or expert_offsets.dim() != 1:
+        raise RuntimeError("Tensor size mismatch!")
+    (M, K), (E, N) = a.shape, b.shape[:2]
+    I = N // 2
+    if M < 1 or E < 1 or N % 2 or I < _FP8_BLOCK or I % _FP8_BLOCK or K < _FP8_BLOCK or K % _FP8_BLOCK:
+        raise ValueError("%s: M_total=%d E=%d 2I=%d K=%d not supported (M_total >= 1, E >= 1, I >= 128 with I %% 128 == 0, K >= 128 with "
+                         "K %% 128 == 0)" % (name, M, E, N, K))
+    _check_dev(a, a_scale, b, b_scale, expert_offsets, h, h_scale)
+    _check_shape(b, E, N, K)
+    _check_shape(a_scale, M, K // _FP8_BLOCK)
+    _check_shape(b_scale, E, N // _FP8_BLOCK, K // _FP8_BLOCK)
+    _check_shape(expert_offsets, E + 1)
+    _check_shape(h, M, I)
+    _check_shape(h_scale, M, I // _FP8_BLOCK)
+    rc = fn(a.data_ptr(), a_scale.data_ptr(), b.data_ptr(), b_scale.data_ptr(), expert_offsets.data_ptr(), h.data_ptr(), h_scale.data_ptr(), M, E,
+            I, K, form_int, 1 if scale_pow2 else 0, _stream())
+    if rc == -2:
+        raise ValueError("%s: M_total=%d E=%d I=%d K=%d too large for one launch" % (name, M, E, I, K))
+    _raise(name, rc)

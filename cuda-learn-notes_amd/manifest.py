@@ -966,3 +966,10 @@ def describe_gemm_fp8_block128_grouped_bf16(M_total, E, N, K, form=None):
     M_total <= 4 E, else tile; "skinny" / "tile" pin one), its grid, the slot count floor(M_total / 128) + E, the empty-expert exit, registers,
     LDS and scratch as text (no GPU needed). ValueError for an unsupported shape or form."""
     return _describe_bf16("cln_gemm_fp8_block128_grouped_bf16", tuple(int(x) for x in (M_total, E, N, K, gemm_fp8_grouped_form(form))), 3072)
+
+
+def describe_gemm_fp8_block128_grouped_swiglu_fp8(M_total, E, I, K, form=None):
+    """describe() for cln_gemm_fp8_block128_grouped_swiglu_fp8 (include/cln_amd_ext.h): the form that runs (form as in
+    describe_gemm_fp8_block128_grouped_bf16), its grid, the slot count, the fused epilogue, registers, LDS and scratch as text (no GPU needed).
+    ValueError for an unsupported shape or form."""
+    return _describe_bf16("cln_gemm_fp8_block128_grouped_swiglu_fp8", tuple(int(x) for x in (M_total, E, I, K, gemm_fp8_grouped_form(form))), 4096)

@@ -908,6 +908,35 @@ int cln_gemm_fp8_block128_grouped_bf16(const void* a, const float* a_scale, cons
                                        void* out, int M_total, int E, int N, int K, int form, void* stream);
 int cln_gemm_fp8_block128_grouped_bf16_describe(int M_total, int E, int N, int K, int form, char* buf, int len);
 
+/* ---- The gate/up projection of an MoE expert FFN with SiLU-mul and the FP8 activation quantiser fused behind it (INTEGRATION.md section
+ * 35). One launch, nothing read on the host, no workspace, no atomics, deterministic, graph-capturable with the offsets
+ * changing between replays.
+ *
+ * cln_gemm_fp8_block128_grouped_swiglu_fp8: a, a_scale, expert_offsets exactly as in cln_gemm_fp8_block128_grouped_bf16 (the same clamp on
+ * the device; empty groups anywhere; a row of no expert is not written); b e4m3fn [E, 2 I, K]: rows 0 ... I - 1 of an expert are its gate
+ * projection, rows I ... 2 I - 1 its up projection; b_scale fp32 [E, 2 I / 128, K / 128]; h e4m3fn [M_total, I]; h_scale fp32
+ * [M_total, I / 128] (the a, a_scale of the down projection: what cln_quant_fp8_block128_bf16 writes); all contiguous. For a row m of expert
+ * e and a column c
+ *     G  = sum_kb a_scale[m, kb] * b_scale[e, c / 128, kb]           * sum_{k in block kb} fp32(a[m, k]) * fp32(b[e, c, k])
+ *     U  = sum_kb a_scale[m, kb] * b_scale[e, I / 128 + c / 128, kb] * sum_{k in block kb} fp32(a[m, k]) * fp32(b[e, I + c, k])
+ * in the arithmetic of cln_gemm_fp8_block128_bf16 (s = a_scale * b_scale, fmaf in ascending kb) but kept in fp32: nothing is rounded to
+ * bf16. hf = (G / (1 + exp(-G))) * U in fp32, the exponential and the reciprocal the hardware's approximate instructions; for G >= 32 the
+ * SiLU factor is G itself. Per row and 128-column block of hf the formula of cln_quant_fp8_block128_bf16: amax = max(amax |hf|, 1e-4f);
+ * scale = amax / 448.0f; if scale_pow2, the smallest power of two >= scale (on the bits); inv = 1.0f / scale; code = e4m3fn, round to
+ * nearest even, of clamp(hf inv, -448, 448); the scale is stored as computed. M_total >= 1; E >= 1; I >= 128 with I % 128 == 0; K >= 128
+ * with K % 128 == 0. Element offsets are 64-bit. form: 0 picks by the rule M_total <= 4 E -> skinny, else tile; 1 pins the skinny form (grid:
+ * I / 128 column blocks x E, 8 waves, two register rings of weights; an empty expert's workgroups return before their first weight load), 2
+ * the tile form (128 rows x 128 columns of h a workgroup over floor(M_total / 128) + E slots, 99328 bytes of LDS); _describe names the
+ * form, its grid and slots, registers and LDS. No NaN code and finite scales: the caller's contract, not checked. Status, in this order:
+ * the shape, or E (skinny) or the slots (tile) above 65535 (-2); a missing pointer, a, b or h not 16-byte aligned, a scale or the offsets not
+ * 4-byte aligned, an output equal to an input or to the other output, scale_pow2 neither 0 nor 1, a form that is none of 0, 1, 2 (-1).
+ * _describe: buf / len (-1), the shape (-2), the form (-1).
+ */
+int cln_gemm_fp8_block128_grouped_swiglu_fp8(const void* a, const float* a_scale, const void* b, const float* b_scale,
+                                             const int* expert_offsets, void* h, float* h_scale, int M_total, int E, int I, int K, int form,
+                                             int scale_pow2, void* stream);
+int cln_gemm_fp8_block128_grouped_swiglu_fp8_describe(int M_total, int E, int I, int K, int form, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
