@@ -77,12 +77,12 @@ EXTRA_FLAGS = {"flash_attn_m16x.hip": ["-fno-slp-vectorize"], "flash_attn_m16x_e
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS.update({"kv_append_paged_mla_bf16_fp8_tile.hip": NO_PACKED_FP32, "flash_attn_decode_paged_mla_sparse_bf16_fp8_tile.hip": NO_PACKED_FP32,
                     "flash_attn_decode_paged_mla_sparse_varlen_bf16_fp8_tile.hip": NO_PACKED_FP32})
-# The block-scaled FP8 GEMM and its quantiser: new units, built without packed fp32 forms like the units above (their
-# fp32 work is the scale-and-add behind each MFMA: 4 v_fma_f32 a sub-tile).
+# The block-scaled FP8 GEMM and its quantiser: built without packed fp32 forms like the units above (their fp32 work is the
+# scale-and-add behind each MFMA: 4 v_fma_f32 a sub-tile). The unit holds the four dense kernels; the bodies are gemm_fp8_block128_core.cuh's.
 EXTRA_FLAGS.update({"gemm_fp8_block128.hip": NO_PACKED_FP32, "quant_fp8_block128_bf16.hip": NO_PACKED_FP32})
-# Its grouped (MoE) sibling includes the dense kernel's header and is built like it.
+# The grouped (MoE) form: the same core header plus gemm_fp8_block128_offsets.cuh, its own two kernels only, the same flags.
 EXTRA_FLAGS.update({"gemm_fp8_block128_grouped.hip": NO_PACKED_FP32})
-# The fused gate/up + SiLU-mul + quantise sibling includes both headers and is built like them.
+# The fused gate/up + SiLU-mul + quantise form: the core, the offsets and fp8_block_scale.cuh, its own two kernels only, the same flags.
 EXTRA_FLAGS.update({"gemm_fp8_block128_grouped_swiglu.hip": NO_PACKED_FP32})
 
 

@@ -33,10 +33,7 @@ CLN_API int cln_gemm_fp8_block128_grouped_bf16_describe(int M_total, int E, int 
   int v = 0, ag = 0;
   g8g_regs(p, &v, &ag);
   char why[96];
-  if (form == g8g::kAuto)
-    snprintf(why, sizeof why, "by the rule: M_total %s %d E", p.tile ? ">" : "<=", g8g::kSkinnyMeanRows);
-  else
-    snprintf(why, sizeof why, "pinned; the rule gives %s", g8g::auto_skinny(M_total, E) ? "skinny" : "tile");
+  g8o::why_form(why, sizeof why, M_total, E, form, p.tile);
   int n;
   if (p.tile)
     n = snprintf(buf, len,

@@ -5,13 +5,17 @@
 //   G  = sum_kb a_scale[m, kb] * b_scale[e, c / 128, kb]           * sum_{k in kb} fp32(a[m, k]) * fp32(b[e, c, k])
 //   U  = sum_kb a_scale[m, kb] * b_scale[e, I / 128 + c / 128, kb] * sum_{k in kb} fp32(a[m, k]) * fp32(b[e, I + c, k])
 //   hf = (G * rcp(1 + exp(-G))) * U                                                                      (fp32; nothing is rounded to bf16)
-// and per row and 128 columns of hf the rule of quant_fp8_block128_bf16.cuh: h e4m3fn [M_total, I], h_scale fp32 [M_total, I / 128] -- the
-// a, a_scale of the down projection. A SIBLING of gemm_fp8_block128_grouped.cuh: G and U are that kernel's sums (gemm_fp8_block128.cuh,
-// included: one g8::mfma128 per scale block with a zero C operand, s = sa * sb, fmaf in ascending kb), the offsets go through the same clamp,
-// and the tile form finds its expert with the same slots and the same search. The grouped header itself is NOT included: it defines its two
-// kernels as plain (non-template) __global__ functions, which one library can hold once, so its clamp, slot rule and search (15 lines) and
-// the constants of its form rule are restated below. What is new is that a workgroup owns the SAME 128 columns of gate and up, so it holds
-// every value a (row, block) scale needs: no workspace, no atomics, no second pass.
+// and per row and 128 columns of hf the rule of quant_fp8_block128_bf16.cuh (the scale: fp8_block_scale.cuh): h e4m3fn [M_total, I], h_scale
+// fp32 [M_total, I / 128] -- the a, a_scale of the down projection. This header owns the two fused kernels with both of their bodies, the
+// SiLU / amax / quantise epilogues, the plan and the launch. G and U are the grouped kernel's sums: one g8::mfma128 per scale block with a
+// zero C operand, s = sa * sb, fmaf in ascending kb (gemm_fp8_block128_core.cuh); the clamp, the slots, the search and the form rule are
+// gemm_fp8_block128_offsets.cuh's (g8o). A workgroup owns the SAME 128 columns of gate and up, so it holds every value a (row, block) scale
+// needs: no workspace, no atomics, no second pass.
+//   Kept here on purpose: the skinny K loop with two weight rows a lane and the two-slot LDS ring with 256 weight rows a slot. Written once in
+//   the core as templates over the rows (a loop over NW in {1, 2}, a ring over WR in {128, 256}) both passed the register gate without a spill
+//   and gave the same bytes, but hipcc scheduled them differently and the MI355X measured them slower than these bodies by more than the
+//   0.1 - 0.3 % run-to-run spread: this skinny form 3 - 5 % at 16 and more chunks an expert, this tile form 7 - 9 % at E = 256, I = 2048,
+//   K = 7168, the dense skinny form 7 - 10 % at M = 64 (profiles/r42_gemm_fp8_block128_core.log).
 //
 // SILU. v_exp_f32 and v_rcp_f32 (approximate, about 1 ulp each). For G >= 32, exp(-G) < 2^-46, 1 + exp(-G) rounds to 1, v_rcp_f32(1) is 1
 // and G * 1 is G: the factor returns G itself, which the exact test stands on. For G < -88 the exponential is +inf, its reciprocal 0.
@@ -35,7 +39,9 @@
 // nothing read on the host, deterministic, graph-capturable with the offsets changing between replays. cln_mfma_keep stands behind every MFMA
 // (inside g8::mfma128). The unit is built without packed fp32 ops (_build.py), and this file writes none.
 #pragma once
-#include "gemm_fp8_block128.cuh"
+#include "fp8_block_scale.cuh"
+#include "gemm_fp8_block128_core.cuh"
+#include "gemm_fp8_block128_offsets.cuh"
 
 namespace g8s {
 
@@ -53,34 +59,8 @@ struct Args {
   int pow2;
 };
 
-// ---- the offsets: the clamp, the first slot of an expert and the search of gemm_fp8_block128_grouped.cuh (g8g), as they stand there
-__device__ __forceinline__ int clamped_offset(const Args& g, int i) { return min(max(g.off[i], 0), g.M); }
-__device__ __forceinline__ unsigned slot_of(int c, int e) { return (unsigned)c / (unsigned)kTileM + (unsigned)e; }
-// The largest e in [0, E) with s_e <= slot, or -1 (a slot in front of the first expert).
-__device__ __forceinline__ int expert_of_slot(const Args& g, unsigned slot) {
-  int lo = 0, hi = g.E;  // s_e <= slot for every e < lo, s_e > slot for every e >= hi
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (slot_of(clamped_offset(g, mid), mid) <= slot)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return __builtin_amdgcn_readfirstlane(lo - 1);
-}
-
 __device__ __forceinline__ float silu_mul(float G, float U) {
   return (G * __builtin_amdgcn_rcpf(1.0f + __expf(-G))) * U;
-}
-
-// The scale of one (row, 128-column block) from its amax: q8::quant_fp8_block128_bf16_rows, statement for statement.
-__device__ __forceinline__ float block_scale(float amax, int pow2) {
-  float scale = fmaxf(amax, 1e-4f) / 448.0f;
-  if (pow2) {
-    const unsigned bits = __float_as_uint(scale);  // positive and normal
-    if (bits & 0x007fffffu) scale = __uint_as_float((bits & 0x7f800000u) + 0x00800000u);
-  }
-  return scale;
 }
 
 // four consecutive codes, byte r = column r: the clamp and the conversion of kva::store_fp8
@@ -185,7 +165,7 @@ __device__ __forceinline__ void skinny(const Args& g, int e, size_t r0, int rows
     float m = 0.0f;
 #pragma unroll
     for (int w = 0; w < kSkinnyWaves; ++w) m = fmaxf(m, red[w * (16 * MT) + 16 * mt + j]);
-    const float scale = block_scale(m, g.pow2);
+    const float scale = cln_fp8_block_scale(m, g.pow2);
     const float inv = 1.0f / scale;
     const unsigned code = pack4(accg[mt], inv);
     if (16 * mt + j < rows) {
@@ -199,13 +179,12 @@ __device__ __forceinline__ void skinny(const Args& g, int e, size_t r0, int rows
 __global__ __launch_bounds__(kSkinnyThreads) void gemm_fp8_block128_grouped_swiglu_skinny_mfma(const Args g) {
   __shared__ float red[2][kSkinnyWaves * kChunk];
   const int e = blockIdx.y;
-  const int c0 = __builtin_amdgcn_readfirstlane(clamped_offset(g, e));
-  const int Me = __builtin_amdgcn_readfirstlane(max(clamped_offset(g, e + 1) - c0, 0));
-  if (Me == 0) return;  // the empty-expert exit: nothing of b[e] has been addressed
+  const g8o::Rows r = g8o::expert_rows(g.off, g.M, e);
+  if (r.Me == 0) return;  // the empty-expert exit: nothing of b[e] has been addressed
   int parity = 0;
-  for (int m0 = 0; m0 < Me; m0 += kChunk, parity ^= 1) {
-    const int rows = min(kChunk, Me - m0);
-    const size_t r0 = (size_t)c0 + (size_t)m0;
+  for (int m0 = 0; m0 < r.Me; m0 += kChunk, parity ^= 1) {
+    const int rows = min(kChunk, r.Me - m0);
+    const size_t r0 = (size_t)r.c0 + (size_t)m0;
     // a wave writes red[parity] again only behind the next chunk's barrier, which every wave reaches after its reads of this chunk
     if (rows <= 16) skinny<1>(g, e, r0, rows, red[parity]);
     else if (rows <= 32) skinny<2>(g, e, r0, rows, red[parity]);
@@ -319,7 +298,7 @@ __device__ __forceinline__ void tile(const Args& g, int e, int c0, int Me, int m
   for (int mt = 0; mt < 4; ++mt) {
     const int mr = m_t + wm + 16 * mt + j;  // relative to the expert; masked at the expert's end
     const float other = lds_ld<float>(lds0 + 4u * (kTileM * ((wave & 1) ^ 1) + wm + 16 * mt + j));
-    const float scale = block_scale(fmaxf(m[mt], other), g.pow2);
+    const float scale = cln_fp8_block_scale(fmaxf(m[mt], other), g.pow2);
     const float inv = 1.0f / scale;
     const size_t row = (size_t)c0 + (size_t)mr;
 #pragma unroll
@@ -333,14 +312,9 @@ __device__ __forceinline__ void tile(const Args& g, int e, int c0, int Me, int m
 
 __global__ __launch_bounds__(256) void gemm_fp8_block128_grouped_swiglu_tile_mfma(const Args g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const unsigned slot = blockIdx.y;
-  const int e = expert_of_slot(g, slot);
-  if (e < 0) return;  // a slot in front of the first expert
-  const int c0 = __builtin_amdgcn_readfirstlane(clamped_offset(g, e));
-  const int Me = __builtin_amdgcn_readfirstlane(max(clamped_offset(g, e + 1) - c0, 0));
-  const unsigned t = slot - slot_of(c0, e);
-  if (t >= (unsigned)((Me + kTileM - 1) / kTileM)) return;  // a slot behind the expert's last tile; uniform, before any barrier
-  tile(g, e, c0, Me, kTileM * (int)t, smem);
+  g8o::Tile w;
+  if (!g8o::tile_of_slot(g.off, g.M, g.E, blockIdx.y, &w)) return;  // uniform, before any barrier
+  tile(g, w.e, w.c0, w.Me, kTileM * w.t, smem);
 }
 
 // ---- the plan: a function of (M_total, E, I, K, form) only (the entry and its describe share it)
@@ -349,30 +323,12 @@ struct Plan {
   unsigned gx, gy;
 };
 
-enum { kAuto = 0, kSkinny = 1, kTile = 2 };
-constexpr long long kMaxGridY = 65535;
-// The rule of form = auto is the grouped entry's (skinny up to a mean group of 4 rows); no measured row has moved it (DESIGN
-// 4.4.30).
-constexpr int kSkinnyMeanRows = 4;
-inline bool auto_skinny(long long M, long long E) { return M <= kSkinnyMeanRows * E; }
-
 // -2 for a shape outside the contract or past one launch in the form chosen; then -1 for a form that is none of 0, 1, 2
 inline int plan(long long M, long long E, long long I, long long K, int form, Plan* p) {
   if (M < 1 || E < 1 || I < kBlock || I % kBlock || K < kBlock || K % kBlock) return CLN_ERR_UNSUPPORTED;
   if (M > 0x7fffffffLL || E > 0x7fffffffLL - 1 || 2 * I > 0x7fffffffLL - 256 || K > 0x7fffffffLL) return CLN_ERR_UNSUPPORTED;
-  const bool known = form == kAuto || form == kSkinny || form == kTile;
   p->gx = (unsigned)(I / kBlock);
-  if (form == kSkinny || (form != kTile && auto_skinny(M, E))) {
-    if (E > kMaxGridY) return CLN_ERR_UNSUPPORTED;
-    p->tile = 0;
-    p->gy = (unsigned)E;
-  } else {
-    const long long slots = M / kTileM + E;
-    if (slots > kMaxGridY) return CLN_ERR_UNSUPPORTED;
-    p->tile = 1;
-    p->gy = (unsigned)slots;
-  }
-  return known ? CLN_OK : CLN_ERR_BAD_ARG;
+  return g8o::plan_form(M, E, form, &p->tile, &p->gy);
 }
 
 inline int launch(const Args& g, const Plan& p, hipStream_t stream) {

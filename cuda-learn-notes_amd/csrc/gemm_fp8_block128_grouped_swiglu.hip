@@ -40,10 +40,7 @@ CLN_API int cln_gemm_fp8_block128_grouped_swiglu_fp8_describe(int M_total, int E
   int v = 0, ag = 0;
   g8s_regs(p, &v, &ag);
   char why[96];
-  if (form == g8s::kAuto)
-    snprintf(why, sizeof why, "by the rule: M_total %s %d E", p.tile ? ">" : "<=", g8s::kSkinnyMeanRows);
-  else
-    snprintf(why, sizeof why, "pinned; the rule gives %s", g8s::auto_skinny(M_total, E) ? "skinny" : "tile");
+  g8o::why_form(why, sizeof why, M_total, E, form, p.tile);
   const long long slots = (long long)M_total / g8::kTileM + E;
   int n;
   if (p.tile)

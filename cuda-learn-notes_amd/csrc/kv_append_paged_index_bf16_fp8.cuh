@@ -11,9 +11,7 @@
 // token means k_d = e4m3(code_d) scale. Every byte that is not a live token's 128 codes or 4 scale bytes keeps its value.
 //
 // Per live token, all in IEEE fp32 (the build has no fast-math; bf16 is exact in fp32):
-//   a     = max(max_d |k_d|, 1e-4f)
-//   scale = a / 448.0f
-//   if pow2: scale = the smallest power of two >= scale -- on the bits: mantissa zero -> unchanged, else exponent + 1, mantissa 0 (no log2)
+//   scale = cln_fp8_block_scale(max_d |k_d|, pow2)                                 (fp8_block_scale.cuh: max(amax, 1e-4) / 448, pow2 on the bits)
 //   inv   = 1.0f / scale
 //   code_d = e4m3fn, round to nearest even, of clamp(k_d inv, -448, 448)          (kva::store_fp8, as it stands)
 // and the scale is stored as computed. Inputs are finite: the caller's contract. scale >= 1e-4 / 448 > 0 always.
@@ -25,6 +23,7 @@
 // tests tok, b, pos or pg only, never j: the 16 lanes of a row leave or stay together, and the moves never cross a row. Every lane then
 // computes the same scale and stores its 8 codes; lane 0 of the row stores the scale. No LDS, no atomics, one launch.
 #pragma once
+#include "fp8_block_scale.cuh"
 #include "kv_append_paged_fp8.cuh"  // store_fp8; kv_append_paged.cuh
 #include "paged_bf16.cuh"
 
@@ -77,11 +76,7 @@ __global__ __launch_bounds__(kThreads) void kv_append_paged_index_bf16_fp8_rows(
   m = fmaxf(m, cln_dpp<0x4E>(m));   // quad_perm [2,3,0,1]
   m = fmaxf(m, cln_dpp<0x141>(m));  // row_half_mirror
   m = fmaxf(m, cln_dpp<0x140>(m));  // row_mirror: the row's amax in its 16 lanes
-  float scale = fmaxf(m, 1e-4f) / 448.0f;
-  if (a.pow2) {
-    const unsigned bits = __float_as_uint(scale);  // positive and normal
-    if (bits & 0x007fffffu) scale = __uint_as_float((bits & 0x7f800000u) + 0x00800000u);
-  }
+  const float scale = cln_fp8_block_scale(m, a.pow2);
   const float inv = 1.0f / scale;
   const size_t r = (size_t)pos & ((1u << a.page_shift) - 1u);
   uint8_t* pagep = a.pool + (size_t)pg * ((size_t)kIdx8RowBytes << a.page_shift);

@@ -9,10 +9,8 @@
 // rows, rows of no sequence untouched, a table entry outside [0, P) stores nothing, q_out may be q. Every pool byte that is not a live
 // token's 656 bytes keeps its value.
 //
-// Per live token and per 128-dim tile of c, all in IEEE fp32, statement for statement what kv_append_paged_index_bf16_fp8.cuh does per token:
-//   a     = max(max_d |c_d|, 1e-4f)
-//   scale = a / 448.0f
-//   if pow2: scale = the smallest power of two >= scale -- on the bits: mantissa zero -> unchanged, else exponent + 1, mantissa 0 (no log2)
+// Per live token and per 128-dim tile of c, all in IEEE fp32, what kv_append_paged_index_bf16_fp8.cuh does per token:
+//   scale = cln_fp8_block_scale(max_d |c_d|, pow2)                                 (fp8_block_scale.cuh: max(amax, 1e-4) / 448, pow2 on the bits)
 //   inv   = 1.0f / scale
 //   code_d = e4m3fn, round to nearest even, of clamp(c_d inv, -448, 448)          (kva::store_fp8, as it stands)
 // and the scale is stored as computed. k_pe is rotated in fp32 and rounded once to bf16 by kva::move_piece<64, ROPE>: the bits the bf16 MLA
@@ -26,6 +24,7 @@
 // with the half-split pairs, which a thread moves two at a time) and then of the Hq query rows, as the bf16 append does. All stores are
 // vector stores; no LDS, no atomics, one launch.
 #pragma once
+#include "fp8_block_scale.cuh"
 #include "kv_append_paged_fp8.cuh"  // store_fp8; kv_append_paged.cuh
 #include "kv_append_paged_mla_bf16.cuh"
 
@@ -96,11 +95,7 @@ __global__ __launch_bounds__(kThreads) void kv_append_paged_mla_bf16_fp8_tile_ro
     m = fmaxf(m, cln_dpp<0x4E>(m));   // quad_perm [2,3,0,1]
     m = fmaxf(m, cln_dpp<0x141>(m));  // row_half_mirror
     m = fmaxf(m, cln_dpp<0x140>(m));  // row_mirror: the tile's amax in its 16 lanes
-    float scale = fmaxf(m, 1e-4f) / 448.0f;
-    if (a.pow2) {
-      const unsigned bits = __float_as_uint(scale);  // positive and normal
-      if (bits & 0x007fffffu) scale = __uint_as_float((bits & 0x7f800000u) + 0x00800000u);
-    }
+    const float scale = cln_fp8_block_scale(m, a.pow2);
     const float inv = 1.0f / scale;
     store_fp8(dst + 8u * u, y, inv);
     if ((u & 15u) == 0u) *(float*)(dst + kMlaTileScaleByte + 4u * (u >> 4)) = scale;

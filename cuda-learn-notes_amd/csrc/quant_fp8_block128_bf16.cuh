@@ -1,11 +1,8 @@
 // The activation quantiser of the block-scaled FP8 GEMM (cln_quant_fp8_block128_bf16, include/cln_amd_ext.h): x bf16 [M, K] ->
 // codes e4m3fn [M, K] and scales fp32 [M, K/128], one scale per row and 128 columns: the A operand of cln_gemm_fp8_block128_bf16.
 //
-// Per row and 128-column block, all in IEEE fp32 -- the formula of kv_append_paged_index_bf16_fp8.cuh and
-// kv_append_paged_mla_bf16_fp8_tile.cuh, statement for statement:
-//   a     = max(max |x|, 1e-4f)
-//   scale = a / 448.0f
-//   if pow2: scale = the smallest power of two >= scale, on the bits
+// Per row and 128-column block, all in IEEE fp32:
+//   scale = cln_fp8_block_scale(max |x|, pow2)                                      (fp8_block_scale.cuh: max(amax, 1e-4) / 448, pow2 on the bits)
 //   inv   = 1.0f / scale
 //   code  = e4m3fn, round to nearest even, of clamp(x inv, -448, 448)              (kva::store_fp8, as it stands)
 // and the scale is stored as computed. Inputs are finite: the caller's contract.
@@ -15,6 +12,7 @@
 // row stores the scale. Block blk = row KB + kb sits at element 128 blk of x and codes and at scales[blk]: the three tensors are contiguous.
 // Bandwidth-bound; no LDS, no atomics, one launch.
 #pragma once
+#include "fp8_block_scale.cuh"
 #include "kv_append_paged_fp8.cuh"  // kva::store_fp8, kva::kThreads
 #include "paged_bf16.cuh"
 
@@ -45,11 +43,7 @@ __global__ __launch_bounds__(kva::kThreads) void quant_fp8_block128_bf16_rows(co
   m = fmaxf(m, cln_dpp<0x4E>(m));   // quad_perm [2,3,0,1]
   m = fmaxf(m, cln_dpp<0x141>(m));  // row_half_mirror
   m = fmaxf(m, cln_dpp<0x140>(m));  // row_mirror: the block's amax in its 16 lanes
-  float scale = fmaxf(m, 1e-4f) / 448.0f;
-  if (a.pow2) {
-    const unsigned bits = __float_as_uint(scale);  // positive and normal
-    if (bits & 0x007fffffu) scale = __uint_as_float((bits & 0x7f800000u) + 0x00800000u);
-  }
+  const float scale = cln_fp8_block_scale(m, a.pow2);
   const float inv = 1.0f / scale;
   kva::store_fp8(a.codes + blk * 128u + 8u * j, y, inv);
   if (j == 0) a.scales[blk] = scale;

@@ -62,9 +62,10 @@ def scan_shared_object(so_path, workdir):
     return out, n_mfma
 
 
-def shared_object_spills(so_path, workdir):
+def shared_object_spills(so_path, workdir, names=None):
     """Kernel metadata of the gfx950 code objects inside a built shared library (llvm-readelf --notes): -> (number of kernels,
-    [(kernel name, vgpr spills, sgpr spills, scratch bytes)] for every kernel that spills or uses scratch)."""
+    [(kernel name, vgpr spills, sgpr spills, scratch bytes)] for every kernel that spills or uses scratch). A list given as `names`
+    receives the name of every kernel, once per code object that holds it."""
     import glob
     import os
     import shutil
@@ -83,6 +84,8 @@ def shared_object_spills(so_path, workdir):
             if not (name and vs and ss and sc):
                 continue
             n += 1
+            if names is not None:
+                names.append(name.group(1))
             if int(vs.group(1)) or int(ss.group(1)) or int(sc.group(1)):
                 bad.append((name.group(1), int(vs.group(1)), int(ss.group(1)), int(sc.group(1))))
     return n, bad

@@ -25,6 +25,20 @@ def test_header_library_package_and_host_hold_the_names(built):
     assert hasattr(built, NAME[4:]) and hasattr(host, NAME[4:]) and hasattr(built.manifest, "describe_" + NAME[4:])
 
 
+def test_the_offsets_layer_and_the_tile_body_are_shared_not_restated():
+    read = lambda fn: open(os.path.join(fs.CSRC, fn)).read()
+    heads = {u: read(u + ".cuh") for u in ("gemm_fp8_block128", "gemm_fp8_block128_grouped", "gemm_fp8_block128_grouped_swiglu")}
+    assert sum("while (lo < hi)" in t for t in heads.values()) == 0 and "while (lo < hi)" in read("gemm_fp8_block128_offsets.cuh")  # one search
+    for u in ("gemm_fp8_block128_grouped", "gemm_fp8_block128_grouped_swiglu"):
+        assert '#include "gemm_fp8_block128_offsets.cuh"' in heads[u] and '#include "gemm_fp8_block128_core.cuh"' in heads[u], u
+        assert '#include "gemm_fp8_block128.cuh"' not in heads[u], u  # the dense header defines the dense kernels
+    for fn in ("gemm_fp8_block128_core.cuh", "gemm_fp8_block128_offsets.cuh", "fp8_block_scale.cuh"):
+        assert "__global__" not in read(fn), fn
+    grouped = heads["gemm_fp8_block128_grouped"]
+    assert "lds_st<u4>" not in grouped and not re.search(r"\bstruct Stage\b", grouped) and not re.search(r"\bvoid tile\(", grouped)
+    assert "g8::tile(" in grouped and re.search(r"\bvoid tile\(const Args& a, int m_t,", read("gemm_fp8_block128_core.cuh"))
+
+
 @pytest.mark.parametrize("M,E,N,K", [(4, 1, 4096, 7168), (5, 1, 4096, 7168), (1024, 256, 7168, 2048), (1025, 256, 264, 384), (280, 7, 264, 384)])
 def test_describe_names_the_form_the_grid_and_the_slots_and_reports_no_scratch(built, M, E, N, K):
     d = built.manifest.describe_gemm_fp8_block128_grouped_bf16

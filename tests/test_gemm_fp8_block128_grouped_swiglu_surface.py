@@ -26,6 +26,16 @@ def test_header_library_package_and_host_hold_the_names(built):
     assert hasattr(built, NAME[4:]) and hasattr(host, NAME[4:]) and hasattr(built.manifest, "describe_" + NAME[4:])
 
 
+def test_the_offsets_layer_and_the_scale_rule_are_included_not_restated():
+    text = open(os.path.join(fs.CSRC, "gemm_fp8_block128_grouped_swiglu.cuh")).read()
+    for inc in ("gemm_fp8_block128_core.cuh", "gemm_fp8_block128_offsets.cuh", "fp8_block_scale.cuh"):
+        assert '#include "%s"' % inc in text, inc
+    assert '#include "gemm_fp8_block128.cuh"' not in text and '#include "kv_append_paged_fp8.cuh"' not in text
+    for restated in ("clamped_offset(const", "slot_of(int", "expert_of_slot(const", "auto_skinny(long", "kSkinnyMeanRows =", "kMaxGridY =", "block_scale(float"):
+        assert restated not in text, restated
+    assert "g8o::tile_of_slot(" in text and "g8o::expert_rows(" in text and "g8o::plan_form(" in text and text.count("cln_fp8_block_scale(") == 2
+
+
 @pytest.mark.parametrize("M,E,I,K", [(4, 1, 2048, 7168), (5, 1, 2048, 7168), (1024, 256, 2048, 7168), (1025, 256, 256, 384), (280, 7, 256, 1024)])
 def test_describe_names_the_form_the_grid_the_slots_and_the_lds_and_reports_no_scratch(built, M, E, I, K):
     d = built.manifest.describe_gemm_fp8_block128_grouped_swiglu_fp8

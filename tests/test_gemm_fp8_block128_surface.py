@@ -57,6 +57,31 @@ def test_unsupported_shapes_are_refused_before_anything_else(built, M, N, K):
             built.quant_fp8_block128_bf16(torch.zeros(M, K, dtype=gr.BF), torch.zeros(M, K).to(gr.F8), torch.zeros(M, kb))
 
 
+def test_the_scale_rule_is_written_in_one_file_under_csrc():
+    holders = [os.path.relpath(os.path.join(d, fn), fs.CSRC) for d, _, fns in os.walk(fs.CSRC) for fn in fns
+               if "1e-4f) / 448.0f" in open(os.path.join(d, fn), errors="replace").read()]
+    assert holders == ["fp8_block_scale.cuh"], holders
+    for u in ("quant_fp8_block128_bf16", "gemm_fp8_block128_grouped_swiglu", "kv_append_paged_index_bf16_fp8", "kv_append_paged_mla_bf16_fp8_tile"):
+        text = open(os.path.join(fs.CSRC, u + ".cuh")).read()
+        assert '#include "fp8_block_scale.cuh"' in text and "cln_fp8_block_scale(" in text, u  # one rule, called by all four
+
+
+def test_the_library_holds_the_four_dense_kernels_once(built, tmp_path):
+    """The grouped units include the kernel-free core header, not the dense header: only the dense unit instantiates the dense kernels."""
+    sys.path.insert(0, os.path.join(fs.ROOT, "cuda-learn-notes_amd", "tools"))
+    import mfma_overlap_scan as scan
+    from cuda_learn_notes_amd import _loader
+    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
+        pytest.skip("llvm-readelf not available")
+    names = []
+    scan.shared_object_spills(_loader.so_path("libcln_amd.so"), str(tmp_path), names)
+    dense = sorted(n for n in names if "gemm_fp8_block128_mfmaILb" in n)
+    assert len(dense) == 4 and len(set(dense)) == 4, dense
+    for form in ("gemm_fp8_block128_grouped_skinny_mfma", "gemm_fp8_block128_grouped_tile_mfma", "gemm_fp8_block128_grouped_swiglu_skinny_mfma",
+                 "gemm_fp8_block128_grouped_swiglu_tile_mfma"):
+        assert sum(form in n for n in names) == 1, form
+
+
 def test_the_helpers_reference_is_dequantise_then_matmul():
     _, a, sa, b, sb, (ref, S) = gr.gaussian(17, 264, 384)
     ad = a.double() * sa.double().repeat_interleave(128, dim=1)
