@@ -754,6 +754,36 @@ def gemm_fp8_block128_grouped_swiglu_fp8(a, a_scale, b, b_scale, expert_offsets,
     return host.gemm_fp8_block128_grouped_swiglu_fp8(a, a_scale, b, b_scale, expert_offsets, h, h_scale, form, scale_pow2)
 
 
+def gemm_mxfp4_bf16(a, a_scale, b, b_scale, out, bias=None, form=None):
+    """MXFP4-weight GEMM on the scaled FP4 x FP8 matrix instruction: a float8_e4m3fn [M,K] with a_scale float8_e8m0fnu
+    [M,K/32] (quant_mxfp8_bf16 writes both), b uint8 [N,K/2] of two e2m1 codes a byte (element 2i in the low nibble of byte i; a gpt-oss
+    `_blocks` tensor viewed so; float4_e2m1fn_x2 accepted) with b_scale float8_e8m0fnu or uint8 [N,K/32], bias bfloat16 [N] or None, out
+    bfloat16 [M,N] = bf16(bias[n] + sum_kb 2^(a_scale-127) 2^(b_scale-127) sum_{k in kb} a[m,k] e2m1(b[n,k])). M >= 1, N % 8 == 0,
+    K % 32 == 0 (ValueError otherwise); form None picks by M <= 64 -> "skinny", else "tile"; either string pins a form. C entry
+    cln_gemm_mxfp4_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.gemm_mxfp4_bf16(a, a_scale, b, b_scale, out, bias, form)
+
+
+def gemm_mxfp4_grouped_bf16(a, a_scale, b, b_scale, expert_offsets, out, bias=None, form=None):
+    """Grouped (MoE) gemm_mxfp4_bf16 in one launch: a float8_e4m3fn [M_total,K] with rows sorted by expert, a_scale
+    float8_e8m0fnu [M_total,K/32], b uint8 [E,N,K/2], b_scale float8_e8m0fnu or uint8 [E,N,K/32], bias bfloat16 [E,N] or None,
+    expert_offsets int32 [E+1] on the GPU (expert e owns rows off[e] ... off[e+1]-1; empty groups allowed; nothing is read on the host), out
+    bfloat16 [M_total,N]: an expert's rows carry the bits of gemm_mxfp4_bf16 on that expert alone; rows of no expert are not written. form
+    None picks by M_total <= 4 E -> "skinny", else "tile"; either string pins a form. C entry cln_gemm_mxfp4_grouped_bf16
+    (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.gemm_mxfp4_grouped_bf16(a, a_scale, b, b_scale, expert_offsets, out, bias, form)
+
+
+def quant_mxfp8_bf16(x, codes, scales):
+    """The activation quantiser of gemm_mxfp4[_grouped]_bf16 (OCP MXFP8): x bfloat16 [M,K] -> codes float8_e4m3fn [M,K] and scales
+    float8_e8m0fnu [M,K/32]; per row and 32 columns the scale byte is clamp(E - 8, 0, 254) with E the exponent field of fp32(amax), code =
+    e4m3fn(clamp(x * 2^(127 - scale byte), +-448)). C entry cln_quant_mxfp8_bf16 (include/cln_amd_ext.h). Not a reference name."""
+    from . import host
+    return host.quant_mxfp8_bf16(x, codes, scales)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

@@ -53,6 +53,7 @@ KERNEL_SOURCES = [
     "flash_attn_decode_paged_mla_sparse_varlen_bf16_fp8_tile.hip",
     "gemm_fp8_block128.hip", "quant_fp8_block128_bf16.hip", "gemm_fp8_block128_grouped.hip",
     "gemm_fp8_block128_grouped_swiglu.hip",
+    "gemm_mxfp4.hip", "gemm_mxfp4_grouped.hip", "quant_mxfp8_bf16.hip",
 ]
 VENDOR_SOURCES = ["hgemm_vendor.hip", "hgemm_vendor_lt.hip", "fa2_vendor_ck.hip", "yardstick_vendor.hip"]  # the last: ck_tile FMHA instances (~1 min of hipcc)
 # a comparison row whose sources are the ROCm image's ck_tile headers: if they are missing or do not compile, the vendor
@@ -84,6 +85,9 @@ EXTRA_FLAGS.update({"gemm_fp8_block128.hip": NO_PACKED_FP32, "quant_fp8_block128
 EXTRA_FLAGS.update({"gemm_fp8_block128_grouped.hip": NO_PACKED_FP32})
 # The fused gate/up + SiLU-mul + quantise form: the core, the offsets and fp8_block_scale.cuh, its own two kernels only, the same flags.
 EXTRA_FLAGS.update({"gemm_fp8_block128_grouped_swiglu.hip": NO_PACKED_FP32})
+# The MXFP4-weight GEMMs and their MXFP8 quantiser: gemm_mxfp4_core.cuh behind the dense and the grouped unit, each its own
+# kernels only; no fp32 work in their K loops, and the same flags as the FP8 family whose headers they include.
+EXTRA_FLAGS.update({"gemm_mxfp4.hip": NO_PACKED_FP32, "gemm_mxfp4_grouped.hip": NO_PACKED_FP32, "quant_mxfp8_bf16.hip": NO_PACKED_FP32})
 
 
 def hipcc():

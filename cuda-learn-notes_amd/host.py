@@ -2332,3 +2332,112 @@ def gemm_fp8_block128_grouped_swiglu_fp8(a, a_scale, b, b_scale, expert_offsets,
     if rc == -2:
         raise ValueError("%s: M_total=%d E=%d I=%d K=%d too large for one launch" % (name, M, E, I, K))
     _raise(name, rc)
+
+
+# ---- the MXFP4-weight GEMMs of gpt-oss' expert FFN and the MXFP8 quantiser of their activations
+_MX_BLOCK = 32
+_MX_SCALE_DTYPES = (torch.float8_e8m0fnu, torch.uint8)
+_MX_FP4_DTYPES = (torch.uint8, torch.float4_e2m1fn_x2)
+
+
+def _check_mx(name, a, a_scale, b, b_scale, out, bias):
+    _check_dtype(a, torch.float8_e4m3fn)
+    _check_dtype(a_scale, torch.float8_e8m0fnu)
+    if b.dtype not in _MX_FP4_DTYPES:
+        raise RuntimeError("values must be uint8 or float4_e2m1fn_x2")
+    if b_scale.dtype not in _MX_SCALE_DTYPES:
+        raise RuntimeError("values must be float8_e8m0fnu or uint8")
+    _check_dtype(out, torch.bfloat16)
+    if bias is not None:
+        _check_dtype(bias, torch.bfloat16)
+
+
+def gemm_mxfp4_bf16(a, a_scale, b, b_scale, out, bias=None, form=None):
+    """out = bias + (a * 2^(a_scale-127)) @ (e2m1(b) * 2^(b_scale-127)).T with OCP MX scales per 32 elements of K, on the scaled FP4 x FP8
+    matrix instruction; one launch, no workspace. a torch.float8_e4m3fn [M,K]; a_scale torch.float8_e8m0fnu [M,K/32] (what
+    quant_mxfp8_bf16 writes); b torch.uint8 (or torch.float4_e2m1fn_x2) [N,K/2], two e2m1 codes a byte, element 2i in the low nibble of byte
+    i; b_scale torch.float8_e8m0fnu (or torch.uint8) [N,K/32]; bias torch.bfloat16 [N] or None, added in fp32 before the one rounding; out
+    torch.bfloat16 [M,N]; all contiguous, on the GPU. form None: "skinny" for M <= 64, else "tile"; "skinny" / "tile" pin a form. M >= 1,
+    N >= 8 with N % 8 == 0, K >= 32 with K % 32 == 0, else ValueError. No scale byte 255 and no NaN code: the caller's contract.
+    Deterministic. C entry cln_gemm_mxfp4_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "gemm_mxfp4_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 4 + [ctypes.c_void_p])
+    form_int = manifest.gemm_fp8_grouped_form(form)
+    _check_mx(name, a, a_scale, b, b_scale, out, bias)
+    if a.dim() != 2 or b.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    (M, K), N = a.shape, b.shape[0]
+    if M < 1 or N < 8 or N % 8 or K < _MX_BLOCK or K % _MX_BLOCK:
+        raise ValueError("%s: M=%d N=%d K=%d not supported (M >= 1, N >= 8 with N %% 8 == 0, K >= 32 with K %% 32 == 0)" % (name, M, N, K))
+    _check_dev(a, a_scale, b, b_scale, out, *(() if bias is None else (bias,)))
+    _check_shape(b, N, K // 2)
+    _check_shape(a_scale, M, K // _MX_BLOCK)
+    _check_shape(b_scale, N, K // _MX_BLOCK)
+    _check_shape(out, M, N)
+    if bias is not None:
+        _check_shape(bias, N)
+    rc = fn(a.data_ptr(), a_scale.data_ptr(), b.data_ptr(), b_scale.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), M, N, K,
+            form_int, _stream())
+    if rc == -2:
+        raise ValueError("%s: M=%d N=%d K=%d too large for one launch" % (name, M, N, K))
+    _raise(name, rc)
+
+
+def gemm_mxfp4_grouped_bf16(a, a_scale, b, b_scale, expert_offsets, out, bias=None, form=None):
+    """gemm_mxfp4_bf16 for every expert of a mixture-of-experts layer in one launch. a torch.float8_e4m3fn [M_total,K], rows
+    sorted by expert; a_scale torch.float8_e8m0fnu [M_total,K/32]; b torch.uint8 (or torch.float4_e2m1fn_x2) [E,N,K/2]; b_scale
+    torch.float8_e8m0fnu (or torch.uint8) [E,N,K/32]; bias torch.bfloat16 [E,N] or None; expert_offsets torch.int32 [E+1] on the GPU: expert
+    e owns the rows off[e] ... off[e+1]-1 (values are clamped to [0,M_total] on the device; empty groups allowed; the host reads none of
+    them); out torch.bfloat16 [M_total,N]; all contiguous, on the GPU. An expert's rows carry the bits of gemm_mxfp4_bf16 on that expert
+    alone; a row of no expert is not written. form None: "skinny" for M_total <= 4 E, else "tile"; "skinny" / "tile" pin a form at any
+    shape. M_total >= 1, E >= 1, N >= 8 with N % 8 == 0, K >= 32 with K % 32 == 0, else ValueError. Deterministic. C entry
+    cln_gemm_mxfp4_grouped_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "gemm_mxfp4_grouped_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 7 + [ctypes.c_int] * 5 + [ctypes.c_void_p])
+    form_int = manifest.gemm_fp8_grouped_form(form)
+    _check_mx(name, a, a_scale, b, b_scale, out, bias)
+    _check_dtype(expert_offsets, torch.int32)
+    if a.dim() != 2 or b.dim() != 3 or expert_offsets.dim() != 1:
+        raise RuntimeError("Tensor size mismatch!")
+    (M, K), (E, N) = a.shape, b.shape[:2]
+    if M < 1 or E < 1 or N < 8 or N % 8 or K < _MX_BLOCK or K % _MX_BLOCK:
+        raise ValueError("%s: M_total=%d E=%d N=%d K=%d not supported (M_total >= 1, E >= 1, N >= 8 with N %% 8 == 0, K >= 32 with "
+                         "K %% 32 == 0)" % (name, M, E, N, K))
+    _check_dev(a, a_scale, b, b_scale, expert_offsets, out, *(() if bias is None else (bias,)))
+    _check_shape(b, E, N, K // 2)
+    _check_shape(a_scale, M, K // _MX_BLOCK)
+    _check_shape(b_scale, E, N, K // _MX_BLOCK)
+    _check_shape(expert_offsets, E + 1)
+    _check_shape(out, M, N)
+    if bias is not None:
+        _check_shape(bias, E, N)
+    rc = fn(a.data_ptr(), a_scale.data_ptr(), b.data_ptr(), b_scale.data_ptr(), None if bias is None else bias.data_ptr(),
+            expert_offsets.data_ptr(), out.data_ptr(), M, E, N, K, form_int, _stream())
+    if rc == -2:
+        raise ValueError("%s: M_total=%d E=%d N=%d K=%d too large for one launch" % (name, M, E, N, K))
+    _raise(name, rc)
+
+
+def quant_mxfp8_bf16(x, codes, scales):
+    """Quantise activations to OCP MXFP8 for gemm_mxfp4[_grouped]_bf16; one launch. x torch.bfloat16 [M,K], K % 32 == 0; codes
+    torch.float8_e4m3fn [M,K]; scales torch.float8_e8m0fnu [M,K/32]; all contiguous, on the GPU. Per row and 32 columns: E = the exponent
+    field of fp32(amax |x|), scale byte = clamp(E - 8, 0, 254), code = e4m3fn(clamp(x * 2^(127 - scale byte), +-448)), round to nearest
+    even. Inputs are finite: the caller's contract. ValueError for M < 1 or another K. Deterministic. C entry cln_quant_mxfp8_bf16
+    (include/cln_amd_ext.h); no CPU path."""
+    name = "quant_mxfp8_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p])
+    _check_dtype(x, torch.bfloat16)
+    _check_dtype(codes, torch.float8_e4m3fn)
+    _check_dtype(scales, torch.float8_e8m0fnu)
+    if x.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    M, K = x.shape
+    if M < 1 or K < _MX_BLOCK or K % _MX_BLOCK:
+        raise ValueError("%s: M=%d K=%d not supported (M >= 1, K >= 32 with K %% 32 == 0)" % (name, M, K))
+    _check_dev(x, codes, scales)
+    _check_shape(codes, M, K)
+    _check_shape(scales, M, K // _MX_BLOCK)
+    rc = fn(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), M, K, _stream())
+    if rc == -2:
+        raise ValueError("%s: M=%d K=%d too large for one launch" % (name, M, K))
+    _raise(name, rc)

@@ -973,3 +973,24 @@ def describe_gemm_fp8_block128_grouped_swiglu_fp8(M_total, E, I, K, form=None):
     describe_gemm_fp8_block128_grouped_bf16), its grid, the slot count, the fused epilogue, registers, LDS and scratch as text (no GPU needed).
     ValueError for an unsupported shape or form."""
     return _describe_bf16("cln_gemm_fp8_block128_grouped_swiglu_fp8", tuple(int(x) for x in (M_total, E, I, K, gemm_fp8_grouped_form(form))), 4096)
+
+
+# The MXFP4-weight GEMMs and their MXFP8 activation quantiser (DESIGN 4.4.32); `form` as in the grouped FP8 entries.
+def describe_gemm_mxfp4_bf16(M, N, K, form=None):
+    """describe() for cln_gemm_mxfp4_bf16 (include/cln_amd_ext.h): the form that runs (form None: skinny for M <= 64, else
+    tile; "skinny" / "tile" pin one) and why, its grid, registers, LDS and scratch as text (no GPU needed). ValueError for an unsupported
+    shape or form."""
+    return _describe_bf16("cln_gemm_mxfp4_bf16", tuple(int(x) for x in (M, N, K, gemm_fp8_grouped_form(form))), 3072)
+
+
+def describe_gemm_mxfp4_grouped_bf16(M_total, E, N, K, form=None):
+    """describe() for cln_gemm_mxfp4_grouped_bf16 (include/cln_amd_ext.h): the form that runs (form None: skinny for
+    M_total <= 4 E, else tile; "skinny" / "tile" pin one), its grid, the slot count floor(M_total / 128) + E, the empty-expert exit,
+    registers, LDS and scratch as text (no GPU needed). ValueError for an unsupported shape or form."""
+    return _describe_bf16("cln_gemm_mxfp4_grouped_bf16", tuple(int(x) for x in (M_total, E, N, K, gemm_fp8_grouped_form(form))), 4096)
+
+
+def describe_quant_mxfp8_bf16(M, K):
+    """describe() for cln_quant_mxfp8_bf16 (include/cln_amd_ext.h): the kernel, the launch and the per-block rule as text (no
+    GPU needed). ValueError for an unsupported shape."""
+    return _describe_bf16("cln_quant_mxfp8_bf16", (int(M), int(K)), 2048)

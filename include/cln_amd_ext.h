@@ -937,6 +937,42 @@ int cln_gemm_fp8_block128_grouped_swiglu_fp8(const void* a, const float* a_scale
                                              int scale_pow2, void* stream);
 int cln_gemm_fp8_block128_grouped_swiglu_fp8_describe(int M_total, int E, int I, int K, int form, char* buf, int len);
 
+/* ---- MXFP4-weight GEMM, dense and grouped, on the scaled FP4 x FP8 matrix instruction, and the MXFP8 activation quantiser that produces its A
+ * operand: the expert FFN format of gpt-oss. All: one launch, no workspace, no atomics,
+ * deterministic, graph-capturable.
+ *
+ * cln_gemm_mxfp4_bf16: a e4m3fn [M, K]; a_scale e8m0 bytes [M, K/32]; b [N, K/2] bytes of two e2m1 codes, element 2 i in the low nibble of
+ * byte i; b_scale e8m0 bytes [N, K/32]; bias bf16 [N] or null; out bf16 [M, N]; all contiguous.
+ *     out[m, n] = bf16_rne( bias[n] + sum_{kb < K/32} 2^(a_scale[m, kb] - 127) 2^(b_scale[n, kb] - 127) sum_{k in block kb} e4m3(a[m, k]) e2m1(b[n, k]) )
+ * 128 k (four MX blocks) per matrix instruction with the scales applied inside it, the fp32 accumulator carried through the instruction from
+ * the bias on; one rounding to bf16 at the end. M >= 1; N >= 8 with N % 8 == 0; K >= 32 with K % 32 == 0 (K % 128 != 0 allowed: 2880). form:
+ * 0 picks by the rule M <= 64 -> skinny (weight nibbles straight to registers), else tile (128 x 128 through LDS); 1, 2 pin one; _describe
+ * names the form and why, its grid, registers and LDS. Element offsets are 64-bit. No scale byte 255 and no NaN code: the caller's contract,
+ * not checked. Status, in this order: the shape (-2); a missing pointer, a, b, out or bias not 16-byte aligned, out equal to an input, a form
+ * that is none of 0, 1, 2 (-1). _describe: buf / len (-1), the shape (-2), the form (-1).
+ *
+ * cln_gemm_mxfp4_grouped_bf16: a, a_scale as above on [M_total, K] rows sorted by expert; b [E, N, K/2]; b_scale [E, N, K/32]; bias bf16
+ * [E, N] or null; expert_offsets int32 [E + 1] in device memory under the contract of cln_gemm_fp8_block128_grouped_bf16: values clamped to
+ * [0, M_total], a group may be empty, nothing is read on the host, a row of no expert is not written, an expert's rows carry the bits of
+ * cln_gemm_mxfp4_bf16 on that expert alone in either form. form: 0 picks by M_total <= 4 E -> skinny, else tile; 1, 2 pin one. Status, in
+ * this order: the shape, or E (skinny) or the slots floor(M_total / 128) + E (tile) above 65535 (-2); a missing pointer, a, b, out or bias
+ * not 16-byte aligned, the offsets not 4-byte aligned, out equal to an input, a form that is none of 0, 1, 2 (-1).
+ *
+ * cln_quant_mxfp8_bf16: x bf16 [M, K], K % 32 == 0 -> codes e4m3fn [M, K], scales e8m0 bytes [M, K/32]. Per row and 32-column block, in
+ * integer and IEEE fp32 operations: E = the biased exponent field of fp32(amax |x|); scale byte = clamp(E - 8, 0, 254) (the OCP MX floor
+ * rule with emax(e4m3) = 8); code = e4m3fn, round to nearest even, of clamp(x 2^(127 - scale byte), -448, 448). amax = 0 gives scale byte 0
+ * and zero codes; a scaled magnitude in (448, 512) saturates to 448. Inputs are finite: the caller's contract. Status, in this order: the
+ * shape (M < 1, K < 32, K % 32 != 0, or M K / 32 past one launch: -2); a missing, misaligned (x, codes 16 bytes) or aliased pointer (-1).
+ */
+int cln_gemm_mxfp4_bf16(const void* a, const void* a_scale, const void* b, const void* b_scale, const void* bias, void* out, int M, int N, int K,
+                        int form, void* stream);
+int cln_gemm_mxfp4_bf16_describe(int M, int N, int K, int form, char* buf, int len);
+int cln_gemm_mxfp4_grouped_bf16(const void* a, const void* a_scale, const void* b, const void* b_scale, const void* bias,
+                                const int* expert_offsets, void* out, int M_total, int E, int N, int K, int form, void* stream);
+int cln_gemm_mxfp4_grouped_bf16_describe(int M_total, int E, int N, int K, int form, char* buf, int len);
+int cln_quant_mxfp8_bf16(const void* x, void* codes, void* scales, int M, int K, void* stream);
+int cln_quant_mxfp8_bf16_describe(int M, int K, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
