@@ -784,6 +784,55 @@ def quant_mxfp8_bf16(x, codes, scales):
     return host.quant_mxfp8_bf16(x, codes, scales)
 
 
+def moe_route_topk(logits, topk_ids, topk_weights, scoring="softmax", bias=None, renormalize=True, scale=1.0):
+    """Top-k routing of a mixture-of-experts layer in one launch: logits bfloat16 or float32 [T,E] -> topk_ids
+    int32 [T,k] (the k largest keys, slot 0 the largest, equal keys to the lower index) and topk_weights float32 [T,k]. scoring "softmax": key
+    = logit, weight = scale exp(l_j - l_max) / sum over the selected (renormalize) or all E experts; "sigmoid": key = sigmoid(l) + bias (float32
+    [E] or None), weight = scale sigmoid(l_j), divided by the selected sum when renormalize. 1 <= E <= 512, 1 <= k <= min(E, 16) (ValueError
+    otherwise; a bias with softmax too). Group-limited selection is not taken. C entry cln_moe_route_topk. Not a reference name."""
+    from . import host
+    return host.moe_route_topk(logits, topk_ids, topk_weights, scoring, bias, renormalize, scale)
+
+
+def moe_sort_plan(n_slots, E):
+    """(blocks, chunk, workspace_bytes) of moe_sort for n_slots = T k slots over E experts (chunk 2048; blocks == 1: one launch, no
+    workspace). C entry cln_moe_sort_plan. Not a reference name."""
+    from . import host
+    return host.moe_sort_plan(n_slots, E)
+
+
+def moe_sort(topk_ids, E, expert_offsets, src, pos, workspace=None):
+    """Stable counting sort of the routing slots by expert: topk_ids int32 [T,k] (an id outside [0,E) is dropped) ->
+    expert_offsets int32 [E+1] (what the grouped GEMMs take), src int32 [T k] (sorted row -> slot t k + j, -1 past the live rows) and pos
+    int32 [T,k] (slot -> row, or -1); workspace of moe_sort_plan's bytes (None when 0). One launch for T k <= 2048, else three; no global
+    atomics, nothing read on the host. C entry cln_moe_sort. Not a reference name."""
+    from . import host
+    return host.moe_sort(topk_ids, E, expert_offsets, src, pos, workspace)
+
+
+def moe_dispatch_fp8_block128_bf16(x, src, k, codes, scales, scale_pow2=False):
+    """Gather and quantise into sorted rows in one launch: row r of codes float8_e4m3fn [rows,K] and scales float32
+    [rows,K/128] carries the bits of quant_fp8_block128_bf16 on row src[r] // k of x bfloat16 [T,K]; a row with src[r] outside [0, T k) is
+    not written. K % 128 == 0 (ValueError otherwise). C entry cln_moe_dispatch_fp8_block128_bf16. Not a reference name."""
+    from . import host
+    return host.moe_dispatch_fp8_block128_bf16(x, src, k, codes, scales, scale_pow2)
+
+
+def moe_dispatch_mxfp8_bf16(x, src, k, codes, scales):
+    """moe_dispatch_fp8_block128_bf16 under quant_mxfp8_bf16's rule: scales float8_e8m0fnu [rows,K/32], K % 32 == 0. C entry
+    cln_moe_dispatch_mxfp8_bf16. Not a reference name."""
+    from . import host
+    return host.moe_dispatch_mxfp8_bf16(x, src, k, codes, scales)
+
+
+def moe_combine_bf16(y, pos, topk_weights, out, residual=None):
+    """out[t] = bf16(residual[t] + sum_j topk_weights[t,j] y[pos[t,j]]) in one launch: y bfloat16 [M_total,N] in sorted rows,
+    pos int32 [T,k] from moe_sort, fp32 fmaf in ascending j, one rounding; a pos outside [0, M_total) contributes nothing. N % 8 == 0, k <= 16
+    (ValueError otherwise). C entry cln_moe_combine_bf16. Not a reference name."""
+    from . import host
+    return host.moe_combine_bf16(y, pos, topk_weights, out, residual)
+
+
 def fa2_attention(q, k, v, causal=False):
     """Differentiable FlashAttention-2 (scale 1/sqrt(D)), layout [B,H,N,D] as torch.nn.functional.scaled_dot_product_attention:
     fp16, D in {64, 128}, N % 256 == 0. Forward fa2_fwd_lse, backward fa2_bwd."""

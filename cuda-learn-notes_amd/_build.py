@@ -54,6 +54,7 @@ KERNEL_SOURCES = [
     "gemm_fp8_block128.hip", "quant_fp8_block128_bf16.hip", "gemm_fp8_block128_grouped.hip",
     "gemm_fp8_block128_grouped_swiglu.hip",
     "gemm_mxfp4.hip", "gemm_mxfp4_grouped.hip", "quant_mxfp8_bf16.hip",
+    "moe_route.hip", "moe_sort.hip", "moe_dispatch.hip", "moe_combine.hip",
 ]
 VENDOR_SOURCES = ["hgemm_vendor.hip", "hgemm_vendor_lt.hip", "fa2_vendor_ck.hip", "yardstick_vendor.hip"]  # the last: ck_tile FMHA instances (~1 min of hipcc)
 # a comparison row whose sources are the ROCm image's ck_tile headers: if they are missing or do not compile, the vendor
@@ -88,6 +89,10 @@ EXTRA_FLAGS.update({"gemm_fp8_block128_grouped_swiglu.hip": NO_PACKED_FP32})
 # The MXFP4-weight GEMMs and their MXFP8 quantiser: gemm_mxfp4_core.cuh behind the dense and the grouped unit, each its own
 # kernels only; no fp32 work in their K loops, and the same flags as the FP8 family whose headers they include.
 EXTRA_FLAGS.update({"gemm_mxfp4.hip": NO_PACKED_FP32, "gemm_mxfp4_grouped.hip": NO_PACKED_FP32, "quant_mxfp8_bf16.hip": NO_PACKED_FP32})
+# The MoE token path: route, sort, dispatch and combine, each unit its own kernels only. The dispatch unit calls the two
+# quantisers' per-block rules from their headers and is built with their flags, so a row gets the same instructions from both; the others
+# take the flag like every unit since 4.4.26.
+EXTRA_FLAGS.update({u: NO_PACKED_FP32 for u in ("moe_route.hip", "moe_sort.hip", "moe_dispatch.hip", "moe_combine.hip")})
 
 
 def hipcc():

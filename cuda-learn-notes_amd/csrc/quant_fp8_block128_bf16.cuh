@@ -26,12 +26,11 @@ struct Args {
   int pow2;
 };
 
-__global__ __launch_bounds__(kva::kThreads) void quant_fp8_block128_bf16_rows(const Args a) {
-  const unsigned long long u = (unsigned long long)blockIdx.x * kva::kThreads + threadIdx.x;
-  const unsigned long long blk = u >> 4;
-  const unsigned j = (unsigned)u & 15u;
-  if (blk >= (unsigned long long)a.blocks) return;
-  const b8 x = *(const b8*)(a.x + blk * 128u + 8u * j);
+// One thread's share of one block, the per-block rule above: 8 columns at x8 / codes8 (the block's start + 8 j, j the lane's place among the
+// block's 16 lanes, which call together); lane 0 of the block stores the scale. The row kernel (quant_fp8_block128_bf16.hip) and the gathering
+// form (moe_dispatch.cuh) both call it, so a row carries the same bits from both. This header defines no kernel.
+__device__ __forceinline__ void quant_piece(const bf16_t* x8, uint8_t* codes8, float* scale_out, unsigned j, int pow2) {
+  const b8 x = *(const b8*)x8;
   float y[8];
   float m = 0.0f;
 #pragma unroll
@@ -43,10 +42,10 @@ __global__ __launch_bounds__(kva::kThreads) void quant_fp8_block128_bf16_rows(co
   m = fmaxf(m, cln_dpp<0x4E>(m));   // quad_perm [2,3,0,1]
   m = fmaxf(m, cln_dpp<0x141>(m));  // row_half_mirror
   m = fmaxf(m, cln_dpp<0x140>(m));  // row_mirror: the block's amax in its 16 lanes
-  const float scale = cln_fp8_block_scale(m, a.pow2);
+  const float scale = cln_fp8_block_scale(m, pow2);
   const float inv = 1.0f / scale;
-  kva::store_fp8(a.codes + blk * 128u + 8u * j, y, inv);
-  if (j == 0) a.scales[blk] = scale;
+  kva::store_fp8(codes8, y, inv);
+  if (j == 0) *scale_out = scale;
 }
 
 // workgroups of the launch, or 0 when the shape does not fit one launch

@@ -3,6 +3,16 @@
 // launch; then -1 for a missing, misaligned (16 bytes; scales 4) or aliased pointer or a scale_pow2 that is neither 0 nor 1.
 #include "quant_fp8_block128_bf16.cuh"
 
+namespace q8 {
+__global__ __launch_bounds__(kva::kThreads) void quant_fp8_block128_bf16_rows(const Args a) {
+  const unsigned long long u = (unsigned long long)blockIdx.x * kva::kThreads + threadIdx.x;
+  const unsigned long long blk = u >> 4;
+  const unsigned j = (unsigned)u & 15u;
+  if (blk >= (unsigned long long)a.blocks) return;
+  quant_piece(a.x + blk * 128u + 8u * j, a.codes + blk * 128u + 8u * j, a.scales + blk, j, a.pow2);
+}
+}  // namespace q8
+
 static int quant_shape(int M, int K, long long* blocks, long long* wgs) {
   if (M < 1 || K < 128 || K % 128) return CLN_ERR_UNSUPPORTED;
   *blocks = (long long)M * (K / 128);

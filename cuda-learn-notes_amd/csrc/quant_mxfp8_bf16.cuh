@@ -25,12 +25,11 @@ struct Args {
   long long blocks;  // M * K / 32
 };
 
-__global__ __launch_bounds__(kva::kThreads) void quant_mxfp8_bf16_rows(const Args a) {
-  const unsigned long long u = (unsigned long long)blockIdx.x * kva::kThreads + threadIdx.x;
-  const unsigned long long blk = u >> 2;
-  const unsigned j = (unsigned)u & 3u;
-  if (blk >= (unsigned long long)a.blocks) return;
-  const b8 x = *(const b8*)(a.x + blk * 32u + 8u * j);
+// One thread's share of one MX block, the per-block rule above: 8 columns at x8 / codes8 (the block's start + 8 j, j the lane's place in the
+// block's quad, whose 4 lanes call together); lane 0 of the quad stores the scale byte. The row kernel (quant_mxfp8_bf16.hip) and the
+// gathering form (moe_dispatch.cuh) both call it, so a row carries the same bits from both. This header defines no kernel.
+__device__ __forceinline__ void quant_piece(const bf16_t* x8, uint8_t* codes8, uint8_t* scale_out, unsigned j) {
+  const b8 x = *(const b8*)x8;
   float y[8];
   float m = 0.0f;
 #pragma unroll
@@ -42,8 +41,8 @@ __global__ __launch_bounds__(kva::kThreads) void quant_mxfp8_bf16_rows(const Arg
   m = fmaxf(m, cln_dpp<0x4E>(m));  // quad_perm [2,3,0,1]: the block's amax in its 4 lanes
   const int scale = min(max((int)((__float_as_uint(m) >> 23) & 0xFFu) - 8, 0), 254);
   const float inv = __uint_as_float(scale < 254 ? (unsigned)(254 - scale) << 23 : 0x00400000u);
-  kva::store_fp8(a.codes + blk * 32u + 8u * j, y, inv);
-  if (j == 0) a.scales[blk] = (uint8_t)scale;
+  kva::store_fp8(codes8, y, inv);
+  if (j == 0) *scale_out = (uint8_t)scale;
 }
 
 // workgroups of the launch, or 0 when the shape does not fit one launch

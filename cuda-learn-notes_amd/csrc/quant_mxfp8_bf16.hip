@@ -3,6 +3,16 @@
 // then -1 for a missing, misaligned (x, codes 16 bytes) or aliased pointer.
 #include "quant_mxfp8_bf16.cuh"
 
+namespace qmx {
+__global__ __launch_bounds__(kva::kThreads) void quant_mxfp8_bf16_rows(const Args a) {
+  const unsigned long long u = (unsigned long long)blockIdx.x * kva::kThreads + threadIdx.x;
+  const unsigned long long blk = u >> 2;
+  const unsigned j = (unsigned)u & 3u;
+  if (blk >= (unsigned long long)a.blocks) return;
+  quant_piece(a.x + blk * 32u + 8u * j, a.codes + blk * 32u + 8u * j, a.scales + blk, j);
+}
+}  // namespace qmx
+
 static int quant_shape(int M, int K, long long* blocks, long long* wgs) {
   if (M < 1 || K < 32 || K % 32) return CLN_ERR_UNSUPPORTED;
   *blocks = (long long)M * (K / 32);

@@ -2441,3 +2441,142 @@ def quant_mxfp8_bf16(x, codes, scales):
     if rc == -2:
         raise ValueError("%s: M=%d K=%d too large for one launch" % (name, M, K))
     _raise(name, rc)
+
+
+# ---- the MoE token path around the grouped GEMMs: route, sort, quantising dispatch, combine
+_MOE_SCORING = {"softmax": 0, "sigmoid": 1}
+
+
+def moe_route_topk(logits, topk_ids, topk_weights, scoring="softmax", bias=None, renormalize=True, scale=1.0):
+    """Top-k routing in one launch. logits torch.bfloat16 or torch.float32 [T,E]; topk_ids torch.int32 [T,k]; topk_weights
+    torch.float32 [T,k]; bias torch.float32 [E] or None, with scoring "sigmoid" only; all contiguous, on the GPU. 1 <= E <= 512, 1 <= k <=
+    min(E, 16), else ValueError. "softmax": the key is the logit, weight = scale * exp(l_j - l_max) / sum over the selected experts
+    (renormalize) or over all E. "sigmoid": s = 1 / (1 + exp(-l)) in fp32, key = s + bias, weight = scale * s_j (/ the sum of the selected s
+    when renormalize). The k largest keys, slot 0 the largest, equal keys to the lower index. Group-limited selection (n_group > 1) is not
+    taken. Finite logits are the caller's contract. Deterministic. C entry cln_moe_route_topk (include/cln_amd_ext.h); no CPU path."""
+    name = "moe_route_topk"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_void_p])
+    if not isinstance(scoring, str) or scoring not in _MOE_SCORING:
+        raise ValueError("%s: scoring must be 'softmax' or 'sigmoid', not %r" % (name, scoring))
+    if bias is not None and scoring != "sigmoid":
+        raise ValueError("%s: a bias goes with scoring 'sigmoid' only" % name)
+    if logits.dtype not in (torch.bfloat16, torch.float32):
+        raise RuntimeError("values must be bfloat16 or float32")
+    _check_dtype(topk_ids, torch.int32)
+    _check_dtype(topk_weights, torch.float32)
+    if bias is not None:
+        _check_dtype(bias, torch.float32)
+    if logits.dim() != 2 or topk_ids.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    (T, E), k = logits.shape, topk_ids.shape[1]
+    if T < 1 or E < 1 or E > 512 or k < 1 or k > min(E, 16):
+        raise ValueError("%s: T=%d E=%d k=%d not supported (T >= 1, 1 <= E <= 512, 1 <= k <= min(E, 16))" % (name, T, E, k))
+    _check_dev(logits, topk_ids, topk_weights, *(() if bias is None else (bias,)))
+    _check_shape(topk_ids, T, k)
+    _check_shape(topk_weights, T, k)
+    if bias is not None:
+        _check_shape(bias, E)
+    _raise(name, fn(logits.data_ptr(), None if bias is None else bias.data_ptr(), topk_ids.data_ptr(), topk_weights.data_ptr(), T, E, k,
+                    1 if logits.dtype == torch.float32 else 0, _MOE_SCORING[scoring], 1 if renormalize else 0, float(scale), _stream()))
+
+
+def moe_sort_plan(n_slots, E):
+    """(blocks, chunk, workspace_bytes) of moe_sort for n_slots = T * k slots over E experts: blocks = ceil(n_slots / chunk) workgroups of
+    chunk = 2048 slots; blocks == 1 is one launch without a workspace, otherwise three launches over an int32 [blocks, E] workspace. ValueError
+    for n_slots < 1, E < 1, E > 65535 or a workspace past 2^28 ints. C entry cln_moe_sort_plan (include/cln_amd_ext.h); runs on the host."""
+    fn = _ext_fn("cln_moe_sort_plan", [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3)
+    n_slots, E = int(n_slots), int(E)
+    if not 0 < n_slots < 2 ** 31 or not 0 < E < 2 ** 31:
+        raise ValueError("moe_sort_plan: n_slots=%d E=%d not supported (1 <= n_slots < 2^31, 1 <= E <= 65535)" % (n_slots, E))
+    blocks, chunk, ws = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
+    rc = fn(n_slots, E, ctypes.addressof(blocks), ctypes.addressof(chunk), ctypes.addressof(ws))
+    if rc != 0:
+        raise ValueError("moe_sort_plan: n_slots=%d E=%d not supported (E <= 65535, blocks * E <= 2^28; status %d)" % (n_slots, E, rc))
+    return blocks.value, chunk.value, ws.value
+
+
+def moe_sort(topk_ids, E, expert_offsets, src, pos, workspace=None):
+    """Stable sort of the routing slots by expert. topk_ids torch.int32 [T,k] (slot s = t*k + j; an id outside [0,E) is a
+    dropped slot); expert_offsets torch.int32 [E+1]: the exclusive prefix of the live counts, what the grouped GEMMs take; src torch.int32
+    [T*k]: sorted row -> slot, -1 from off[E] on; pos torch.int32 [T,k]: slot -> sorted row, or -1; workspace: a contiguous GPU tensor of at
+    least moe_sort_plan(T*k, E)[2] bytes (None allowed when that is 0). Within an expert the rows are in ascending s. One launch when T*k <=
+    2048, else three; no global atomics, nothing read on the host. ValueError for an empty topk_ids or an unsupported E. Deterministic. C
+    entry cln_moe_sort (include/cln_amd_ext.h); no CPU path."""
+    name = "moe_sort"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 2 + [ctypes.c_void_p])
+    for t in (topk_ids, expert_offsets, src, pos):
+        _check_dtype(t, torch.int32)
+    n = topk_ids.numel()
+    _, _, ws_bytes = moe_sort_plan(n, E)
+    _check_dev(topk_ids, expert_offsets, src, pos, *(() if workspace is None else (workspace,)))
+    _check_shape(expert_offsets, E + 1)
+    _check_shape(src, n)
+    _check_shape(pos, *topk_ids.shape)
+    if ws_bytes and (workspace is None or workspace.numel() * workspace.element_size() < ws_bytes):
+        raise RuntimeError("%s: workspace of %d bytes needed (moe_sort_plan)" % (name, ws_bytes))
+    _raise(name, fn(topk_ids.data_ptr(), expert_offsets.data_ptr(), src.data_ptr(), pos.data_ptr(),
+                    None if workspace is None else workspace.data_ptr(), n, int(E), _stream()))
+
+
+def _moe_dispatch(name, block, scale_dtype, x, src, k, codes, scales, pow2):
+    _check_dtype(x, torch.bfloat16)
+    _check_dtype(src, torch.int32)
+    _check_dtype(codes, torch.float8_e4m3fn)
+    _check_dtype(scales, scale_dtype)
+    if x.dim() != 2 or src.dim() != 1:
+        raise RuntimeError("Tensor size mismatch!")
+    (T, K), rows, k = x.shape, src.shape[0], int(k)
+    if rows < 1 or T < 1 or k < 1 or K < block or K % block or K > 2 ** 20 or T * k >= 2 ** 31:
+        raise ValueError("%s: rows=%d T=%d k=%d K=%d not supported (all >= 1, K %% %d == 0, K <= 2^20, T k < 2^31)" % (name, rows, T, k, K, block))
+    _check_dev(x, src, codes, scales)
+    _check_shape(codes, rows, K)
+    _check_shape(scales, rows, K // block)
+    return rows, T, k, K
+
+
+def moe_dispatch_fp8_block128_bf16(x, src, k, codes, scales, scale_pow2=False):
+    """Gather and quantise in one launch: x torch.bfloat16 [T,K]; src torch.int32 [rows] from moe_sort (rows = T*k); codes
+    torch.float8_e4m3fn [rows,K]; scales fp32 [rows,K/128]; all contiguous, on the GPU. Row r carries the bits quant_fp8_block128_bf16 gives
+    for row src[r] // k of x; a row with src[r] outside [0, T*k) is not written. K % 128 == 0, else ValueError. Deterministic. C entry
+    cln_moe_dispatch_fp8_block128_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "moe_dispatch_fp8_block128_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 + [ctypes.c_void_p])
+    rows, T, k, K = _moe_dispatch(name, _FP8_BLOCK, torch.float32, x, src, k, codes, scales, scale_pow2)
+    _raise(name, fn(x.data_ptr(), src.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, T, k, K, 1 if scale_pow2 else 0, _stream()))
+
+
+def moe_dispatch_mxfp8_bf16(x, src, k, codes, scales):
+    """moe_dispatch_fp8_block128_bf16 for the MXFP4-weight GEMMs: scales torch.float8_e8m0fnu [rows,K/32], row r the bits quant_mxfp8_bf16
+    gives for row src[r] // k of x; K % 32 == 0, else ValueError. C entry cln_moe_dispatch_mxfp8_bf16 (include/cln_amd_ext.h); no CPU path."""
+    name = "moe_dispatch_mxfp8_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_void_p])
+    rows, T, k, K = _moe_dispatch(name, _MX_BLOCK, torch.float8_e8m0fnu, x, src, k, codes, scales, False)
+    _raise(name, fn(x.data_ptr(), src.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, T, k, K, _stream()))
+
+
+def moe_combine_bf16(y, pos, topk_weights, out, residual=None):
+    """out[t] = bf16(residual[t] + sum_j topk_weights[t,j] * y[pos[t,j]]) in one launch: y torch.bfloat16 [M_total,N] (the down
+    projection's output, sorted rows); pos torch.int32 [T,k] from moe_sort; topk_weights fp32 [T,k]; residual torch.bfloat16 [T,N] or None;
+    out torch.bfloat16 [T,N]; all contiguous, on the GPU. fp32, one fmaf a term in ascending j, one rounding to nearest even; a pos outside
+    [0, M_total) contributes nothing. N % 8 == 0 and k <= 16, else ValueError. Deterministic. C entry cln_moe_combine_bf16
+    (include/cln_amd_ext.h); no CPU path."""
+    name = "moe_combine_bf16"
+    fn = _ext_fn("cln_" + name, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 4 + [ctypes.c_void_p])
+    _check_dtype(y, torch.bfloat16)
+    _check_dtype(pos, torch.int32)
+    _check_dtype(topk_weights, torch.float32)
+    _check_dtype(out, torch.bfloat16)
+    if residual is not None:
+        _check_dtype(residual, torch.bfloat16)
+    if y.dim() != 2 or pos.dim() != 2:
+        raise RuntimeError("Tensor size mismatch!")
+    (M, N), (T, k) = y.shape, pos.shape
+    if M < 1 or T < 1 or N < 8 or N % 8 or N > 2 ** 22 or k < 1 or k > 16:
+        raise ValueError("%s: M_total=%d T=%d N=%d k=%d not supported (all >= 1, N %% 8 == 0, N <= 2^22, k <= 16)" % (name, M, T, N, k))
+    _check_dev(y, pos, topk_weights, out, *(() if residual is None else (residual,)))
+    _check_shape(topk_weights, T, k)
+    _check_shape(out, T, N)
+    if residual is not None:
+        _check_shape(residual, T, N)
+    _raise(name, fn(y.data_ptr(), pos.data_ptr(), topk_weights.data_ptr(), None if residual is None else residual.data_ptr(), out.data_ptr(),
+                    M, T, N, k, _stream()))

@@ -994,3 +994,40 @@ def describe_quant_mxfp8_bf16(M, K):
     """describe() for cln_quant_mxfp8_bf16 (include/cln_amd_ext.h): the kernel, the launch and the per-block rule as text (no
     GPU needed). ValueError for an unsupported shape."""
     return _describe_bf16("cln_quant_mxfp8_bf16", (int(M), int(K)), 2048)
+
+
+# The MoE token path (DESIGN 4.4.33): route, sort (and its plan), the two quantising dispatches, combine.
+def describe_moe_route_topk(T, E, k, logits_fp32=False, scoring="softmax", renormalize=True):
+    """describe() for cln_moe_route_topk (include/cln_amd_ext.h): the kernel instantiation, the grid, the keys a lane holds, the
+    rounds and the weight formula as text (no GPU needed). ValueError for an unsupported shape or scoring."""
+    if scoring not in ("softmax", "sigmoid"):
+        raise ValueError("scoring must be 'softmax' or 'sigmoid', not %r" % (scoring,))
+    return _describe_bf16("cln_moe_route_topk", (int(T), int(E), int(k), int(bool(logits_fp32)), int(scoring == "sigmoid"), int(bool(renormalize))), 2048)
+
+
+def describe_moe_sort(n_slots, E):
+    """describe() for cln_moe_sort (include/cln_amd_ext.h): blocks, the chunk, the launches (1, or 3 over the workspace), the
+    kernels with their grids and LDS as text (no GPU needed). ValueError for an unsupported shape."""
+    return _describe_bf16("cln_moe_sort", (int(n_slots), int(E)), 2048)
+
+
+def describe_moe_sort_plan(n_slots, E):
+    """describe() for cln_moe_sort_plan: the text of describe_moe_sort under the plan's name."""
+    return _describe_bf16("cln_moe_sort_plan", (int(n_slots), int(E)), 2048)
+
+
+def describe_moe_dispatch_fp8_block128_bf16(rows, T, k, K, scale_pow2=False):
+    """describe() for cln_moe_dispatch_fp8_block128_bf16 (include/cln_amd_ext.h): the kernel, the grid, the row map and the
+    quantiser whose rule it includes as text (no GPU needed). ValueError for an unsupported shape."""
+    return _describe_bf16("cln_moe_dispatch_fp8_block128_bf16", (int(rows), int(T), int(k), int(K), int(bool(scale_pow2))), 2048)
+
+
+def describe_moe_dispatch_mxfp8_bf16(rows, T, k, K):
+    """describe() for cln_moe_dispatch_mxfp8_bf16 (include/cln_amd_ext.h), as describe_moe_dispatch_fp8_block128_bf16."""
+    return _describe_bf16("cln_moe_dispatch_mxfp8_bf16", (int(rows), int(T), int(k), int(K)), 2048)
+
+
+def describe_moe_combine_bf16(M_total, T, N, k):
+    """describe() for cln_moe_combine_bf16 (include/cln_amd_ext.h): the kernel, the grid, the loads and the sum's order as text
+    (no GPU needed). ValueError for an unsupported shape."""
+    return _describe_bf16("cln_moe_combine_bf16", (int(M_total), int(T), int(N), int(k)), 2048)

@@ -973,6 +973,54 @@ int cln_gemm_mxfp4_grouped_bf16_describe(int M_total, int E, int N, int K, int f
 int cln_quant_mxfp8_bf16(const void* x, void* codes, void* scales, int M, int K, void* stream);
 int cln_quant_mxfp8_bf16_describe(int M, int K, char* buf, int len);
 
+/* ---- The MoE token path around the grouped GEMMs: top-k routing, the stable expert sort that
+ * makes expert_offsets, the quantising dispatch into sorted rows and the weighted combine back to tokens. All: the caller passes every
+ * output and the workspace, the host reads no device value, no global atomics, deterministic, graph-capturable; every kernel compiles to 0
+ * bytes of scratch. A slot is s = t k + j (token t, choice j), n_slots = T k. Status of every entry, in this order: a non-positive dim (-1);
+ * an unsupported or too-large shape (-2), before any launch; a missing, misaligned or aliased pointer or a flag that is neither 0 nor 1 (-1).
+ * _describe: buf / len (-1), then the same.
+ *
+ * cln_moe_route_topk: logits bf16 (logits_fp32 0) or fp32 (1) [T, E]; bias fp32 [E] or null, with scoring 1 only; topk_ids int32 [T, k];
+ * topk_weights fp32 [T, k]. 1 <= E <= 512, 1 <= k <= min(E, 16), else -2; a bias with scoring 0: -2. scoring 0 (softmax): key = the logit;
+ * weight = scale exp(l_j - l_max) / sum, the sum over the selected experts (renormalize 1) or over all E (0). scoring 1 (sigmoid): s = 1 /
+ * (1 + exp(-l)) in fp32, key = s + bias; weight = scale s_j, divided by the sum of the selected s when renormalize. The k largest keys, slot
+ * 0 the largest, equal keys to the lower index. Group-limited selection (n_group > 1) is not taken. Finite logits are the caller's contract.
+ * One wave a token, keys in registers, k wave-wide arg-max rounds; one launch.
+ *
+ * cln_moe_sort_plan: blocks = ceil(n_slots / chunk), chunk = 2048, workspace_bytes = 0 for blocks == 1, else 4 blocks E. E <= 65535 and
+ * blocks E <= 2^28, else -2.
+ * cln_moe_sort: topk_ids int32 [n_slots]; an id outside [0, E) is a dropped slot (-1 for a masked token, another rank's expert).
+ * expert_offsets int32 [E + 1]: the exclusive prefix of the live counts, off[E] the live slots. src int32 [n_slots]: sorted row r < off[E]
+ * holds its slot, the rows from off[E] on hold -1. pos int32 [n_slots]: the row of slot s, or -1. Stable: within an expert the rows are in
+ * ascending s. workspace: workspace_bytes of the plan, 4-byte aligned (not read for blocks == 1; may be null then). blocks == 1: one launch;
+ * else three on the stream (histograms, scan, ranks); no workgroup waits on another inside a launch.
+ *
+ * cln_moe_dispatch_fp8_block128_bf16 / cln_moe_dispatch_mxfp8_bf16: x bf16 [T, K]; src int32 [rows] (cln_moe_sort's, rows = n_slots); codes
+ * e4m3fn [rows, K]; scales fp32 [rows, K/128], respectively e8m0 bytes [rows, K/32]. Row r carries the bits that cln_quant_fp8_block128_bf16
+ * (cln_quant_mxfp8_bf16) gives for row src[r] / k of x; a row with src[r] outside [0, T k) is not written (tested on the device). K % 128
+ * == 0 (K % 32 == 0), K <= 2^20 and T k < 2^31, else -2. x and codes 16-byte aligned. One launch.
+ *
+ * cln_moe_combine_bf16: y bf16 [M_total, N]; pos int32 [T, k] (cln_moe_sort's); topk_weights fp32 [T, k]; residual bf16 [T, N] or null; out
+ * bf16 [T, N] = bf16_rne(residual[t] + sum_j w[t, j] y[pos[t, j]]) in fp32, one fmaf a term in ascending j, one rounding. A pos outside
+ * [0, M_total) contributes nothing. N % 8 == 0, N <= 2^22, k <= 16, else -2. y, residual, out 16-byte aligned; out equal to an input: -1.
+ * One launch.
+ */
+int cln_moe_route_topk(const void* logits, const float* bias, int* topk_ids, float* topk_weights, int T, int E, int k, int logits_fp32,
+                       int scoring, int renormalize, float scale, void* stream);
+int cln_moe_route_topk_describe(int T, int E, int k, int logits_fp32, int scoring, int renormalize, char* buf, int len);
+int cln_moe_sort_plan(int n_slots, int E, int* blocks, int* chunk, long long* workspace_bytes);
+int cln_moe_sort_plan_describe(int n_slots, int E, char* buf, int len);
+int cln_moe_sort(const int* topk_ids, int* expert_offsets, int* src, int* pos, void* workspace, int n_slots, int E, void* stream);
+int cln_moe_sort_describe(int n_slots, int E, char* buf, int len);
+int cln_moe_dispatch_fp8_block128_bf16(const void* x, const int* src, void* codes, float* scales, int rows, int T, int k, int K, int scale_pow2,
+                                       void* stream);
+int cln_moe_dispatch_fp8_block128_bf16_describe(int rows, int T, int k, int K, int scale_pow2, char* buf, int len);
+int cln_moe_dispatch_mxfp8_bf16(const void* x, const int* src, void* codes, void* scales, int rows, int T, int k, int K, void* stream);
+int cln_moe_dispatch_mxfp8_bf16_describe(int rows, int T, int k, int K, char* buf, int len);
+int cln_moe_combine_bf16(const void* y, const int* pos, const float* topk_weights, const void* residual, void* out, int M_total, int T, int N,
+                         int k, void* stream);
+int cln_moe_combine_bf16_describe(int M_total, int T, int N, int k, char* buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
